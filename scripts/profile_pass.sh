@@ -21,5 +21,5 @@ echo sq ok
 python3 tools/pmc_summary.py $OUT --config C3 > $OUT/pmc_summary.log 2>&1 || { echo "pmc_summary rc=$?"; tail -5 $OUT/pmc_summary.log; exit 1; }
 cp profiles/pmc_summary.json $OUT/pmc_summary.json
 echo pmc summary restamped
-timeout -k 10 500 python3 bench.py > $OUT/bench_default.log 2>&1 || { echo "bench rc=$?"; tail -5 $OUT/bench_default.log; exit 1; }
+timeout -k 10 500 python3 bench.py --full > $OUT/bench_default.log 2>&1 || { echo "bench rc=$?"; tail -5 $OUT/bench_default.log; exit 1; }
 tail -1 $OUT/bench_default.log | cut -c1-300

@@ -6,7 +6,7 @@ set -u
 TAG=${1:-r6full}
 bash scripts/full_pass.sh $TAG || exit 1
 cd "$GRAFT_REPO_ROOT" && O=gpurun_out/$TAG
-timeout -k 10 500 python -u bench.py --gpus 8 --dist-backend gloo --config C3 --steps 2 --warmup 1 --timeout 420 \
+timeout -k 10 500 python -u bench.py --full --gpus 8 --dist-backend gloo --config C3 --steps 2 --warmup 1 --timeout 420 \
   > $O/self8_C3.log 2>&1 || { echo "self8 C3 failed"; tail -5 $O/self8_C3.log; exit 1; }
 python3 -c "
 import json;l=[json.loads(x) for x in open('$O/self8_C3.log') if x.startswith('{')][-1]
