@@ -11,8 +11,10 @@ package is the host-side mirror of the reference's interface for that path:
   merkle   MerkleTreeWithCap, Poseidon2Sponge (TreeHasher)  (cs/oracle/*)
   commit   witness_commit, CommitWorkspace                   (prover.rs:313-353)
   sharded  multi-GPU commit (one process per GPU)
+  deep     precompute_for_barycentric_evaluation_in_extension, barycentric_evaluate_*,
+           quotening_operation_in_extension                  (utils.rs:907-1200, prover.rs:1501-2050, 2523-2706)
 """
 from ._lib import BoojumError, load  # noqa: F401
 from .field import P, GENERATOR  # noqa: F401
 
-__all__ = ["fft", "lde", "merkle", "commit", "field", "BoojumError", "load", "P", "GENERATOR"]
+__all__ = ["fft", "lde", "merkle", "commit", "deep", "field", "BoojumError", "load", "P", "GENERATOR"]

@@ -1,0 +1,419 @@
+// DEEP: evaluations at the out-of-domain point and the quotening pass that builds the FRI codeword.
+//
+// * bj_barycentric_weights_d: precompute_for_barycentric_evaluation_in_extension
+//   (cs/implementations/utils.rs:907-1021), the Lagrange weights of coset * <w_n> at an Ext2 point.
+// * bj_evaluate_at_d: barycentric_evaluate_base_at_extension_for_bitreversed_parallel
+//   (utils.rs:1085-1158) for many columns at once, the sums of prover.rs:1501-1780.
+// * bj_deep_quotient_d: one opening point of quotening_operation_in_extension
+//   (prover.rs:2523-2706, driven by :1823-2050) over a row window of the flat bit-reversed domain.
+//
+// GoldilocksExt2 is (c0, c1) with u^2 = 7 (field/goldilocks/extension.rs:14-40).  The kernels see
+// base columns only: the caller folds every source of an opening point, base or Ext2, into one
+// Ext2 coefficient per base column and one Ext2 constant, so
+//   sum_j ch_j (f_j(x) - v_j) = sum_c gamma_c col_c(x) - K.
+// Field arithmetic is exact, so any order of operations gives the reference's bits once the
+// outputs are canonical.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include "gl.hpp"
+#include "gl_asm.hpp"
+#include "bj_internal.hpp"
+#include "../../include/boojum_mi355x.h"
+
+namespace bj {
+
+namespace {
+
+constexpr uint64_t EXT2_NON_RESIDUE = 7;  // GoldilocksExt2::NON_RESIDUE (extension.rs:14-16)
+static_assert(EXT2_NON_RESIDUE == (1u << 3) - 1, "times7 multiplies by the non-residue as 2^3 v - v");
+
+__host__ __device__ __forceinline__ uint64_t times7(uint64_t v) { return gl::sub(gl::mul_pow2_small(v, 3), v); }
+__host__ __device__ __forceinline__ uint64_t neg(uint64_t v) { return gl::sub(0, v); }
+
+// a^(p - 2), p - 2 = (2^31 - 1) 2^33 + (2^32 - 1): 64 squarings and 10 products
+__device__ __forceinline__ uint64_t sqn(uint64_t a, int k) {
+    for (int i = 0; i < k; i++) a = gl::mul(a, a);
+    return a;
+}
+__device__ uint64_t inv_chain(uint64_t a) {
+    const uint64_t t2 = gl::mul(sqn(a, 1), a);       // a^(2^2 - 1)
+    const uint64_t t4 = gl::mul(sqn(t2, 2), t2);     // a^(2^4 - 1)
+    const uint64_t t8 = gl::mul(sqn(t4, 4), t4);
+    const uint64_t t16 = gl::mul(sqn(t8, 8), t8);
+    const uint64_t t24 = gl::mul(sqn(t16, 8), t8);
+    const uint64_t t28 = gl::mul(sqn(t24, 4), t4);
+    const uint64_t t30 = gl::mul(sqn(t28, 2), t2);
+    const uint64_t t31 = gl::mul(sqn(t30, 1), a);    // a^(2^31 - 1)
+    const uint64_t t32 = gl::mul(sqn(t31, 1), a);    // a^(2^32 - 1)
+    return gl::mul(sqn(t31, 33), t32);
+}
+
+// Powers of one root w by 8-bit digits of the exponent: tab[256 k + b] = w^(b 2^(8k)), k < 4, and
+// the digit-0 entries carry `scale` as well, so scale * w^e is three products for any e < 2^32.
+constexpr uint32_t POW_TAB_WORDS = 1024;
+__global__ __launch_bounds__(256) void pow_table_kernel(uint64_t* __restrict__ tab, uint64_t w, uint64_t scale) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t k = t >> 8, b = t & 255;
+    uint64_t v = gl::pow(w, (uint64_t)b << (8 * k));
+    if (k == 0) v = gl::mul(v, scale);
+    tab[t] = gl::canon(v);
+}
+__device__ __forceinline__ uint64_t scaled_pow(const uint64_t* __restrict__ tab, uint32_t e) {
+    const uint64_t lo = gl::mul(tab[e & 255], tab[256 + ((e >> 8) & 255)]);
+    const uint64_t hi = gl::mul(tab[512 + ((e >> 16) & 255)], tab[768 + (e >> 24)]);
+    return gl::mul(lo, hi);
+}
+
+// ------------------------------------------------------------------ barycentric weights
+// w[bitrev_n(i)] = C' y / (at - y), y = coset w_n^i (tab), C' = (at^n - coset^n) / (n coset^n);
+// the Ext2 inverse is conj / norm with one base inverse per element.  s7 = 7 at1^2.
+__global__ __launch_bounds__(256) void weights_kernel(const uint64_t* __restrict__ tab, uint32_t log_n, uint64_t c0,
+                                                      uint64_t c1, uint64_t at0, uint64_t at1, uint64_t s7,
+                                                      uint64_t* __restrict__ w0, uint64_t* __restrict__ w1) {
+    const size_t n = (size_t)1 << log_n;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint64_t y = scaled_pow(tab, (uint32_t)i);
+        const uint64_t d0 = gl::sub(at0, y);
+        const uint64_t ninv = inv_chain(gl::sub(gl::mul(d0, d0), s7));
+        const uint64_t i0 = gl::mul(d0, ninv), i1 = gl::mul(neg(at1), ninv);  // 1 / (at - y)
+        const uint64_t t0 = gl::mul(c0, y), t1 = gl::mul(c1, y);
+        const size_t r = gl::bitrev32((uint32_t)i, log_n);
+        w0[r] = gl::canon(gl::add(gl::mul(t0, i0), times7(gl::mul(t1, i1))));
+        w1[r] = gl::canon(gl::add(gl::mul(t0, i1), gl::mul(t1, i0)));
+    }
+}
+__global__ void weights_one_kernel(uint64_t* __restrict__ w0, uint64_t* __restrict__ w1) {
+    w0[0] = 1;
+    w1[0] = 0;
+}
+
+// ------------------------------------------------------------------ evaluate at z
+// The sum over the four waves of a 256-thread block, in every thread.  Every thread of the block calls it.
+__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* ws) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v = gl::add(v, (uint64_t)__shfl_down((unsigned long long)v, d, 64));
+    __syncthreads();  // the previous sum's readers are done with ws
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return gl::add(gl::add(ws[0], ws[1]), gl::add(ws[2], ws[3]));
+}
+
+// Block (x = column tile, y = row range) sums rows [y rpb, (y + 1) rpb) of EVAL_TC columns: a thread
+// keeps the weights of its row in registers across the tile's columns (two products per element)
+// and its partial sums in registers across its rows; one block sum per column at the end.  Column
+// tiles of one row range are neighbours in the grid, so the weights they share come from cache.
+// partial: [row range][column][2], not canonical.
+constexpr uint32_t EVAL_TC = 8;
+constexpr size_t EVAL_MIN_ROWS = 1024;  // rows per block: at least four per thread
+__global__ __launch_bounds__(256) void evaluate_partial_kernel(const uint64_t* __restrict__ cols, uint32_t n_cols,
+                                                               size_t col_stride, size_t n, size_t rpb,
+                                                               const uint64_t* __restrict__ w0,
+                                                               const uint64_t* __restrict__ w1,
+                                                               uint64_t* __restrict__ partial) {
+    __shared__ uint64_t ws[4];
+    const uint32_t c0 = blockIdx.x * EVAL_TC;
+    const uint32_t nc = n_cols - c0 < EVAL_TC ? n_cols - c0 : EVAL_TC;
+    const size_t start = (size_t)blockIdx.y * rpb;
+    const size_t end = start + rpb < n ? start + rpb : n;
+    const uint64_t* base = cols + (size_t)c0 * col_stride;
+    uint64_t s0[EVAL_TC], s1[EVAL_TC];
+#pragma unroll
+    for (uint32_t j = 0; j < EVAL_TC; j++) s0[j] = s1[j] = 0;
+    for (size_t r = start + threadIdx.x; r < end; r += 256) {
+        const uint64_t a = w0[r], b = w1[r];
+        const uint32_t al = (uint32_t)a, ah = (uint32_t)(a >> 32), bl = (uint32_t)b, bh = (uint32_t)(b >> 32);
+        uint64_t f[EVAL_TC];
+#pragma unroll
+        for (uint32_t j = 0; j < EVAL_TC; j++) f[j] = j < nc ? base[(size_t)j * col_stride + r] : 0;
+#pragma unroll
+        for (uint32_t j = 0; j < EVAL_TC; j += 2) {
+            const uint32_t fl = (uint32_t)f[j], fh = (uint32_t)(f[j] >> 32);
+            const uint32_t gl_ = (uint32_t)f[j + 1], gh = (uint32_t)(f[j + 1] >> 32);
+            uint32_t zl[4], zh[4];
+            glasm::mul_x4(fl, fh, al, ah, zl[0], zh[0], fl, fh, bl, bh, zl[1], zh[1],
+                          gl_, gh, al, ah, zl[2], zh[2], gl_, gh, bl, bh, zl[3], zh[3]);
+            s0[j] = gl::add(s0[j], ((uint64_t)zh[0] << 32) | zl[0]);
+            s1[j] = gl::add(s1[j], ((uint64_t)zh[1] << 32) | zl[1]);
+            s0[j + 1] = gl::add(s0[j + 1], ((uint64_t)zh[2] << 32) | zl[2]);
+            s1[j + 1] = gl::add(s1[j + 1], ((uint64_t)zh[3] << 32) | zl[3]);
+        }
+    }
+    uint64_t* out = partial + ((size_t)blockIdx.y * n_cols + c0) * 2;
+#pragma unroll
+    for (uint32_t j = 0; j < EVAL_TC; j++) {
+        if (j < nc) {  // block-uniform
+            const uint64_t t0 = block_sum(s0[j], ws), t1 = block_sum(s1[j], ws);
+            if (threadIdx.x == 0) {
+                out[2 * j] = t0;
+                out[2 * j + 1] = t1;
+            }
+        }
+    }
+}
+
+// One block per column: the sum over the row ranges in a fixed order, canonical.
+__global__ __launch_bounds__(256) void evaluate_finish_kernel(const uint64_t* __restrict__ partial, uint32_t n_cols,
+                                                              uint32_t n_ranges, uint64_t* __restrict__ out) {
+    __shared__ uint64_t ws[4];
+    const uint32_t c = blockIdx.x;
+    uint64_t a0 = 0, a1 = 0;
+    for (uint32_t b = threadIdx.x; b < n_ranges; b += 256) {
+        a0 = gl::add(a0, partial[((size_t)b * n_cols + c) * 2]);
+        a1 = gl::add(a1, partial[((size_t)b * n_cols + c) * 2 + 1]);
+    }
+    const uint64_t t0 = block_sum(a0, ws), t1 = block_sum(a1, ws);
+    if (threadIdx.x == 0) {
+        out[2 * (size_t)c] = gl::canon(t0);
+        out[2 * (size_t)c + 1] = gl::canon(t1);
+    }
+}
+
+// ------------------------------------------------------------------ quotening
+// acc += f * (g0, g1) for the two rows of a pair; the coefficient is wave-uniform (SGPRs)
+__device__ __forceinline__ void fma_pair(uint64_t fe, uint64_t fo, uint64_t g0, uint64_t g1, uint64_t (&acc)[4]) {
+    uint32_t zl[4], zh[4];
+    const uint32_t el = (uint32_t)fe, eh = (uint32_t)(fe >> 32), ol = (uint32_t)fo, oh = (uint32_t)(fo >> 32);
+    const uint32_t g0l = (uint32_t)g0, g0h = (uint32_t)(g0 >> 32), g1l = (uint32_t)g1, g1h = (uint32_t)(g1 >> 32);
+    glasm::mul_sb_x4(el, eh, g0l, g0h, zl[0], zh[0], el, eh, g1l, g1h, zl[1], zh[1],
+                     ol, oh, g0l, g0h, zl[2], zh[2], ol, oh, g1l, g1h, zl[3], zh[3]);
+#pragma unroll
+    for (int i = 0; i < 4; i++) acc[i] = gl::add(acc[i], ((uint64_t)zh[i] << 32) | zl[i]);
+}
+
+// A thread owns the rows (2i, 2i + 1) of global pair i: in the bit-reversed domain they are the
+// points (x, -x), x = 7 w_N^(bitrev_{log N - 1}(i)) (tab), so the two Ext2 inverses 1 / (+-x - at) share
+// one base inverse: norms (x - at0)^2 - 7 at1^2 and (x + at0)^2 - 7 at1^2, one inversion of their
+// product.  Lanes are consecutive pairs, so a column's load is contiguous over the wave; the
+// columns are looped with the coefficient table read through a uniform index.  V16: the window
+// starts and ends on a pair and every column is 16-byte aligned, so a pair is one 16-byte load and
+// store; otherwise 8-byte accesses, each row checked against the window.
+constexpr uint32_t DQ_UNROLL = 8;
+template <bool V16>
+__global__ __launch_bounds__(256) void deep_quotient_kernel(
+    const uint64_t* __restrict__ cols, uint32_t n_cols, size_t col_stride, const uint64_t* __restrict__ gammas,
+    uint64_t k0, uint64_t k1, uint64_t at0, uint64_t at1, uint64_t s7, const uint64_t* __restrict__ tab,
+    uint32_t pair_bits, size_t row0, size_t n_rows, size_t n_pairs, uint64_t* __restrict__ dst0,
+    uint64_t* __restrict__ dst1, int accumulate) {
+    const size_t t = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (t >= n_pairs) return;
+    const size_t pair = (row0 >> 1) + t;
+    // window-relative index of the pair's even row (-1 when the window starts on an odd row)
+    const ptrdiff_t rel = (ptrdiff_t)(2 * pair) - (ptrdiff_t)row0;
+    const bool in_e = V16 || (rel >= 0 && (size_t)rel < n_rows);
+    const bool in_o = V16 || (size_t)(rel + 1) < n_rows;
+    auto load = [&](const uint64_t* col, uint64_t& fe, uint64_t& fo) {
+        if constexpr (V16) {
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(col + rel);
+            fe = v.x;
+            fo = v.y;
+        } else {
+            fe = in_e ? col[rel] : 0;
+            fo = in_o ? col[rel + 1] : 0;
+        }
+    };
+    uint64_t acc[4] = {0, 0, 0, 0};  // even row (c0, c1), odd row (c0, c1)
+    uint32_t c = 0;
+    for (; c + DQ_UNROLL <= n_cols; c += DQ_UNROLL) {  // DQ_UNROLL columns' loads in flight per lane
+        uint64_t fe[DQ_UNROLL], fo[DQ_UNROLL];
+#pragma unroll
+        for (uint32_t j = 0; j < DQ_UNROLL; j++) load(cols + (size_t)(c + j) * col_stride, fe[j], fo[j]);
+#pragma unroll
+        for (uint32_t j = 0; j < DQ_UNROLL; j++) fma_pair(fe[j], fo[j], gammas[2 * (c + j)], gammas[2 * (c + j) + 1], acc);
+    }
+    for (; c < n_cols; c++) {
+        uint64_t fe, fo;
+        load(cols + (size_t)c * col_stride, fe, fo);
+        fma_pair(fe, fo, gammas[2 * c], gammas[2 * c + 1], acc);
+    }
+    const uint64_t x = scaled_pow(tab, gl::bitrev32((uint32_t)pair, pair_bits));
+    const uint64_t de = gl::sub(x, at0), xa = gl::add(x, at0);  // the odd row's c0 is -xa
+    uint64_t ne = gl::sub(gl::mul(de, de), s7), no = gl::sub(gl::mul(xa, xa), s7);
+    if (!in_e) ne = 1;  // a row outside the window (or the domain) must not enter the shared inverse
+    if (!in_o) no = 1;
+    const uint64_t inv = inv_chain(gl::mul(ne, no));
+    const uint64_t ie = gl::mul(inv, no), io = gl::mul(inv, ne);
+    // 1 / (d0 - at1 u) = (d0 + at1 u) / norm
+    const uint64_t e0 = gl::mul(de, ie), e1 = gl::mul(at1, ie);
+    const uint64_t o0 = gl::mul(neg(xa), io), o1 = gl::mul(at1, io);
+    const uint64_t me0 = gl::sub(acc[0], k0), me1 = gl::sub(acc[1], k1);
+    const uint64_t mo0 = gl::sub(acc[2], k0), mo1 = gl::sub(acc[3], k1);
+    uint64_t qe0 = gl::add(gl::mul(me0, e0), times7(gl::mul(me1, e1)));
+    uint64_t qe1 = gl::add(gl::mul(me0, e1), gl::mul(me1, e0));
+    uint64_t qo0 = gl::add(gl::mul(mo0, o0), times7(gl::mul(mo1, o1)));
+    uint64_t qo1 = gl::add(gl::mul(mo0, o1), gl::mul(mo1, o0));
+    if constexpr (V16) {
+        ulonglong2* p0 = reinterpret_cast<ulonglong2*>(dst0 + rel);
+        ulonglong2* p1 = reinterpret_cast<ulonglong2*>(dst1 + rel);
+        if (accumulate) {
+            const ulonglong2 a = *p0, b = *p1;
+            qe0 = gl::add(qe0, a.x);
+            qo0 = gl::add(qo0, a.y);
+            qe1 = gl::add(qe1, b.x);
+            qo1 = gl::add(qo1, b.y);
+        }
+        *p0 = make_ulonglong2(gl::canon(qe0), gl::canon(qo0));
+        *p1 = make_ulonglong2(gl::canon(qe1), gl::canon(qo1));
+    } else {
+        if (in_e) {
+            if (accumulate) {
+                qe0 = gl::add(qe0, dst0[rel]);
+                qe1 = gl::add(qe1, dst1[rel]);
+            }
+            dst0[rel] = gl::canon(qe0);
+            dst1[rel] = gl::canon(qe1);
+        }
+        if (in_o) {
+            if (accumulate) {
+                qo0 = gl::add(qo0, dst0[rel + 1]);
+                qo1 = gl::add(qo1, dst1[rel + 1]);
+            }
+            dst0[rel + 1] = gl::canon(qo0);
+            dst1[rel + 1] = gl::canon(qo1);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ launchers
+struct Ext2 {
+    uint64_t c0, c1;
+};
+Ext2 ext_mul(Ext2 a, Ext2 b) {
+    return {gl::add(gl::mul(a.c0, b.c0), times7(gl::mul(a.c1, b.c1))), gl::add(gl::mul(a.c0, b.c1), gl::mul(a.c1, b.c0))};
+}
+
+// stream-ordered scratch from the library's pool, freed on the same stream when it goes out of scope
+struct Scratch {
+    uint64_t* p = nullptr;
+    hipStream_t st;
+    explicit Scratch(hipStream_t s) : st(s) {}
+    hipError_t alloc(size_t words) { return pool_alloc((void**)&p, words * 8, st); }
+    ~Scratch() {
+        if (p) (void)hipFreeAsync(p, st);
+    }
+};
+
+hipError_t launch_pow_table(uint64_t* tab, uint64_t w, uint64_t scale, hipStream_t st) {
+    hipLaunchKernelGGL(pow_table_kernel, dim3(POW_TAB_WORDS / 256), dim3(256), 0, st, tab, w, scale);
+    return hipGetLastError();
+}
+
+hipError_t launch_weights(uint32_t log_n, uint64_t coset, uint64_t at0, uint64_t at1, uint64_t* w0, uint64_t* w1,
+                          hipStream_t st) {
+    if (log_n == 0) {  // n == 1: (1, 0) (utils.rs:919-927)
+        hipLaunchKernelGGL(weights_one_kernel, dim3(1), dim3(1), 0, st, w0, w1);
+        return hipGetLastError();
+    }
+    const size_t n = (size_t)1 << log_n;
+    // C' = (at^n - coset^n) / (n coset^n) (utils.rs:933-945 without the factor coset, which the kernel's y carries)
+    coset = gl::canon(coset);
+    Ext2 an{gl::canon(at0), gl::canon(at1)};
+    uint64_t cn = coset;
+    for (uint32_t i = 0; i < log_n; i++) {
+        an = ext_mul(an, an);
+        cn = gl::mul(cn, cn);
+    }
+    const uint64_t k = gl::inv(gl::mul(cn, gl::canon((uint64_t)n)));
+    const uint64_t c0 = gl::canon(gl::mul(gl::sub(an.c0, cn), k)), c1 = gl::canon(gl::mul(an.c1, k));
+    const uint64_t s7 = gl::canon(times7(gl::mul(at1, at1)));
+    Scratch tab(st);
+    if (hipError_t e = tab.alloc(POW_TAB_WORDS)) return e;
+    if (hipError_t e = launch_pow_table(tab.p, gl::domain_generator(log_n), coset, st)) return e;
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(weights_kernel, dim3((unsigned)blocks), dim3(256), 0, st, tab.p, log_n, c0, c1, gl::canon(at0),
+                       gl::canon(at1), s7, w0, w1);
+    return hipGetLastError();
+}
+
+hipError_t launch_evaluate_at(const uint64_t* cols, uint32_t n_cols, size_t col_stride, uint32_t log_n,
+                              const uint64_t* w0, const uint64_t* w1, uint64_t* out, hipStream_t st) {
+    if (n_cols == 0) return hipSuccess;
+    const size_t n = (size_t)1 << log_n;
+    const uint32_t tiles = (n_cols + EVAL_TC - 1) / EVAL_TC;
+    // about 4096 blocks, at most 1024 row ranges (a power of two, so the ranges are equal)
+    size_t max_ranges = 1;
+    while (max_ranges < 1024 && max_ranges * 2 * tiles <= 4096) max_ranges *= 2;
+    size_t rpb = n / max_ranges;
+    if (rpb < EVAL_MIN_ROWS) rpb = EVAL_MIN_ROWS;
+    const size_t ranges = (n + rpb - 1) / rpb;
+    Scratch partial(st);
+    if (hipError_t e = partial.alloc(ranges * n_cols * 2)) return e;
+    hipLaunchKernelGGL(evaluate_partial_kernel, dim3(tiles, (unsigned)ranges), dim3(256), 0, st, cols, n_cols,
+                       col_stride, n, rpb, w0, w1, partial.p);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(evaluate_finish_kernel, dim3(n_cols), dim3(256), 0, st, partial.p, n_cols, (uint32_t)ranges, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_deep_quotient(const uint64_t* cols, uint32_t n_cols, size_t col_stride, const uint64_t* gammas,
+                                uint64_t k0, uint64_t k1, uint64_t at0, uint64_t at1, uint32_t log_domain, size_t row0,
+                                size_t n_rows, uint64_t* dst0, uint64_t* dst1, int accumulate, hipStream_t st) {
+    if (n_rows == 0) return hipSuccess;
+    at0 = gl::canon(at0);
+    at1 = gl::canon(at1);
+    const uint64_t s7 = gl::canon(times7(gl::mul(at1, at1)));
+    Scratch tab(st);
+    if (hipError_t e = tab.alloc(POW_TAB_WORDS)) return e;
+    if (hipError_t e = launch_pow_table(tab.p, gl::domain_generator(log_domain), gl::GENERATOR, st)) return e;
+    const uint32_t pair_bits = log_domain ? log_domain - 1 : 0;
+    const size_t n_pairs = ((row0 + n_rows + 1) >> 1) - (row0 >> 1);
+    const size_t blocks = (n_pairs + 255) / 256;  // at most 2^23
+    uintptr_t align = (uintptr_t)dst0 | (uintptr_t)dst1;
+    if (n_cols) align |= (uintptr_t)cols;
+    const bool v16 = (row0 & 1) == 0 && (n_rows & 1) == 0 && align % 16 == 0 && (n_cols <= 1 || (col_stride & 1) == 0);
+    auto kernel = v16 ? deep_quotient_kernel<true> : deep_quotient_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, cols, n_cols, col_stride, gammas,
+                       gl::canon(k0), gl::canon(k1), at0, at1, s7, tab.p, pair_bits, row0, n_rows, n_pairs, dst0, dst1,
+                       accumulate);
+    return hipGetLastError();
+}
+
+int hip_error(hipError_t e, const char* what) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
+    return set_error(BJ_EHIP, msg);
+}
+
+}  // namespace
+
+}  // namespace bj
+
+extern "C" {
+
+int bj_barycentric_weights_d(uint32_t log_n, uint64_t coset, uint64_t at0, uint64_t at1, uint64_t* w0, uint64_t* w1,
+                             void* stream) {
+    if (log_n > 32) return bj::set_error(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
+    if (!w0 || !w1) return bj::set_error(BJ_EINVAL, "bj_barycentric_weights_d: null output");
+    if (gl::canon(coset) == 0) return bj::set_error(BJ_EINVAL, "bj_barycentric_weights_d: coset must be non-zero");
+    const hipError_t e = bj::launch_weights(log_n, coset, at0, at1, w0, w1, reinterpret_cast<hipStream_t>(stream));
+    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "barycentric weights");
+}
+
+int bj_evaluate_at_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride, uint32_t log_n, const uint64_t* w0,
+                     const uint64_t* w1, uint64_t* out, void* stream) {
+    if (log_n > 32) return bj::set_error(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
+    if (n_cols == 0) return BJ_OK;
+    if (!cols || !w0 || !w1 || !out) return bj::set_error(BJ_EINVAL, "bj_evaluate_at_d: null pointer");
+    if (col_stride < ((size_t)1 << log_n)) return bj::set_error(BJ_EINVAL, "bj_evaluate_at_d: col_stride < 2^log_n");
+    const hipError_t e =
+        bj::launch_evaluate_at(cols, n_cols, col_stride, log_n, w0, w1, out, reinterpret_cast<hipStream_t>(stream));
+    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "evaluate at");
+}
+
+int bj_deep_quotient_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride, const uint64_t* gammas, uint64_t k0,
+                       uint64_t k1, uint64_t at0, uint64_t at1, uint32_t log_domain, size_t row0, size_t n_rows,
+                       uint64_t* dst0, uint64_t* dst1, int accumulate, void* stream) {
+    if (log_domain > 32) return bj::set_error(BJ_EINVAL, "log_domain exceeds the 2-adicity (32) of the field");
+    const size_t domain = (size_t)1 << log_domain;
+    if (n_rows > domain || row0 > domain - n_rows)
+        return bj::set_error(BJ_EINVAL, "bj_deep_quotient_d: row0 + n_rows exceeds 2^log_domain");
+    if (n_rows == 0) return BJ_OK;
+    if (!dst0 || !dst1) return bj::set_error(BJ_EINVAL, "bj_deep_quotient_d: null dst");
+    if (n_cols && (!cols || !gammas)) return bj::set_error(BJ_EINVAL, "bj_deep_quotient_d: null cols or gammas");
+    if (n_cols && col_stride < n_rows) return bj::set_error(BJ_EINVAL, "bj_deep_quotient_d: col_stride < n_rows");
+    const hipError_t e = bj::launch_deep_quotient(cols, n_cols, col_stride, gammas, k0, k1, at0, at1, log_domain, row0,
+                                                  n_rows, dst0, dst1, accumulate, reinterpret_cast<hipStream_t>(stream));
+    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "deep quotient");
+}
+
+}  // extern "C"

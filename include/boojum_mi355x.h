@@ -473,6 +473,53 @@ int bj_fri_fold_d(const uint64_t* c0, const uint64_t* c1, size_t n_src, const ui
                   uint64_t coset_inverse, uint64_t ch0, uint64_t ch1, uint64_t* dst_c0, uint64_t* dst_c1,
                   void* stream);
 
+/* ------------------------------------------------------------------ DEEP */
+/* Evaluations at the out-of-domain point z and the quotening pass that builds the codeword
+ * bj_fri_fold_d folds, on LDE columns that stay on the device.  Added after 2.6; detect by symbol
+ * (bj_abi_version() is unchanged).  Device pointers are stream-ordered.  GoldilocksExt2 values
+ * are pairs (c0, c1) with u^2 = 7 (field/goldilocks/extension.rs:14-40); outputs are canonical. */
+
+/* precompute_for_barycentric_evaluation_in_extension(n, coset, at), utils.rs:907-1021:
+ * w[bitrev_n(i)] = C * w_n^i / (at - coset * w_n^i),  C = coset * (at^n - coset^n) / (n * coset^n)
+ * w0, w1: n words each (the Ext2 halves), canonical.  log_n = 0: (1, 0).
+ * BJ_EINVAL: log_n > 32, a null output, coset = 0.  Precondition (the reference's own, its batch
+ * inverse at utils.rs:983; not checked): at is no point of coset * <w_n>. */
+int bj_barycentric_weights_d(uint32_t log_n, uint64_t coset, uint64_t at0, uint64_t at1,
+                             uint64_t* w0, uint64_t* w1, void* stream);
+
+/* barycentric_evaluate_base_at_extension_for_bitreversed_parallel (utils.rs:1085-1158) for n_cols
+ * columns at once, the per-polynomial sums of prover.rs:1501-1780:
+ * out[2c], out[2c+1] = sum_r cols[c*col_stride + r] * (w0[r], w1[r]), r < 2^log_n, canonical.
+ * (Columns are coset 0 of bj_lde_d's output: col_stride = D * n.)  An Ext2 polynomial held as two
+ * base columns is e0 + u * e1 of its columns' results (utils.rs:1160-1200).  Per-block partial
+ * sums go through the library's stream-ordered pool and a second launch adds them in a fixed
+ * order: no atomics.  BJ_EINVAL: log_n > 32, a null pointer with n_cols > 0, col_stride < 2^log_n. */
+int bj_evaluate_at_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride, uint32_t log_n,
+                     const uint64_t* w0, const uint64_t* w1, uint64_t* out, void* stream);
+
+/* One opening point of quotening_operation_in_extension (prover.rs:2523-2706, driven by
+ * :1823-2050) over rows [row0, row0 + n_rows) of the flat bit-reversed domain of 2^log_domain
+ * points (leaf order L = coset * n + row):
+ *   x_L = 7 * w_{2^log_domain}^{bitrev(L)}
+ *   q   = (sum_c gammas[c] * cols[c*col_stride + (L - row0)] - (k0, k1)) / (x_L - (at0, at1))
+ *   dst0/dst1[L - row0] = q (accumulate = 0) or += q (accumulate = 1), canonical.
+ * gammas: device, n_cols x 2.  cols and dst are window-relative, so a rank that holds only its
+ * leaf range (bj_lde_shard_d's layout) calls it unchanged.  n_cols = 0 is legal (q = -K/(x - at)).
+ * The caller folds the sources f_j, values v_j and challenge powers ch_j of the opening point into
+ * the coefficients: a base source adds ch_j to its column's gamma, an Ext2 source (c0, c1) adds
+ * ch_j to the c0 column's and ch_j * u to the c1 column's, and K = sum_j ch_j * v_j, so
+ * sum_j ch_j (f_j(x) - v_j) = sum_c gamma_c col_c(x) - K (the "c1 is None" branch of
+ * prover.rs:2523-2539 is the base case).  n_rows = 0 is a no-op.  BJ_EINVAL: log_domain > 32,
+ * row0 + n_rows > 2^log_domain, a null dst, null cols or gammas with n_cols > 0, col_stride <
+ * n_rows.  Precondition (the reference's own, not checked): x - at != 0 on the whole domain, that
+ * is, at is no point of 7 * <w_{2^log_domain}>.  A window that starts and ends on an even row with
+ * 16-byte-aligned cols and dst and an even col_stride moves each (x, -x) row pair as one 16-byte
+ * access; any other window runs the same arithmetic with 8-byte accesses. */
+int bj_deep_quotient_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride, const uint64_t* gammas,
+                       uint64_t k0, uint64_t k1, uint64_t at0, uint64_t at1, uint32_t log_domain,
+                       size_t row0, size_t n_rows, uint64_t* dst0, uint64_t* dst1, int accumulate,
+                       void* stream);
+
 /* ------------------------------------------------------------- utility */
 
 /* Batched field arithmetic through the device field layer (utility for parity tests of
