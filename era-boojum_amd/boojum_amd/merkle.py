@@ -27,80 +27,59 @@ def _hp(a):
     return a.ctypes.data_as(_u64p)
 
 
-class Poseidon2Sponge:
-    """TreeHasher<GoldilocksField> for GoldilocksPoseidon2Sponge<AbsorptionModeOverwrite>
-    (host-call forms; the batched device forms are the tree kernels)."""
+def _tree_hasher(name, doc, f_leaf, f_node):
+    """The host TreeHasher<GoldilocksField> class of one hasher: its two *_h seams (host-call
+    forms; the batched device forms are the tree kernels).  Digests are 4 u64 words; for the
+    byte-output hashers they are the 32 digest bytes, little-endian (`digest_bytes`)."""
 
-    @staticmethod
     def hash_into_leaf(elements):
         e = as_u64_host(elements)
         out = np.zeros(4, dtype=np.uint64)
-        call("bj_hash_into_leaf_h", _hp(e) if e.size else None, e.size, _hp(out))
+        call(f_leaf, _hp(e) if e.size else None, e.size, _hp(out))
         return out
 
-    @staticmethod
     def hash_into_node(left, right, depth=0):
         out = np.zeros(4, dtype=np.uint64)
-        call("bj_hash_into_node_h", _hp(as_u64_host(left)), _hp(as_u64_host(right)), _hp(out))
+        call(f_node, _hp(as_u64_host(left)), _hp(as_u64_host(right)), _hp(out))
         return out
 
-    @staticmethod
-    def poseidon2_permutation(state):
-        s = as_u64_host(state).copy()
-        if s.size != 12:
-            raise ValueError("state must have 12 elements")
-        call("bj_poseidon2_permute_h", _hp(s))
-        return s
-
-
-class Blake2s256:
-    """TreeHasher<GoldilocksField> for blake2::Blake2s256 (host-call forms). Digests are 32
-    bytes as 4 little-endian u64 words (`digest_bytes` gives the bytes)."""
-
-    @staticmethod
-    def hash_into_leaf(elements):
-        e = as_u64_host(elements)
-        out = np.zeros(4, dtype=np.uint64)
-        call("bj_blake2s_leaf_h", _hp(e) if e.size else None, e.size, _hp(out))
-        return out
-
-    @staticmethod
-    def hash_into_node(left, right, depth=0):
-        out = np.zeros(4, dtype=np.uint64)
-        call("bj_blake2s_node_h", _hp(as_u64_host(left)), _hp(as_u64_host(right)), _hp(out))
-        return out
-
-    @staticmethod
     def digest_bytes(words):
         return np.asarray(words, dtype=np.uint64).astype("<u8").tobytes()
 
-
-class Keccak256:
-    """TreeHasher<GoldilocksField> for sha3::Keccak256 (host-call forms), cs/oracle/mod.rs:247-313.
-    Digests are 32 bytes as 4 little-endian u64 words."""
-
-    @staticmethod
-    def hash_into_leaf(elements):
-        e = as_u64_host(elements)
-        out = np.zeros(4, dtype=np.uint64)
-        call("bj_keccak256_leaf_h", _hp(e) if e.size else None, e.size, _hp(out))
-        return out
-
-    @staticmethod
-    def hash_into_node(left, right, depth=0):
-        out = np.zeros(4, dtype=np.uint64)
-        call("bj_keccak256_node_h", _hp(as_u64_host(left)), _hp(as_u64_host(right)), _hp(out))
-        return out
-
-    digest_bytes = Blake2s256.digest_bytes
+    return type(name, (), {"__doc__": "TreeHasher<GoldilocksField> for " + doc,
+                           "hash_into_leaf": staticmethod(hash_into_leaf),
+                           "hash_into_node": staticmethod(hash_into_node),
+                           "digest_bytes": staticmethod(digest_bytes)})
 
 
-# hasher name -> (host TreeHasher, leaves, chunked leaves, nodes entry points)
+def _row(name, doc, f_leaves, f_chunked, f_nodes, f_leaf, f_node):
+    return (_tree_hasher(name, doc, f_leaf, f_node), f_leaves, f_chunked, f_nodes, f_leaf, f_node)
+
+
+# hasher name -> (host TreeHasher, leaves, chunked leaves, nodes entry points, leaf and node seams)
 HASHERS = {
-    "poseidon2": (Poseidon2Sponge, "bj_merkle_leaves_d", "bj_merkle_leaves_chunked_d", "bj_merkle_nodes_d"),
-    "blake2s": (Blake2s256, "bj_blake2s_leaves_d", "bj_blake2s_leaves_chunked_d", "bj_blake2s_nodes_d"),
-    "keccak256": (Keccak256, "bj_keccak256_leaves_d", "bj_keccak256_leaves_chunked_d", "bj_keccak256_nodes_d"),
+    "poseidon2": _row("Poseidon2Sponge", "GoldilocksPoseidon2Sponge<AbsorptionModeOverwrite>, cs/oracle/mod.rs:114-175",
+                      "bj_merkle_leaves_d", "bj_merkle_leaves_chunked_d", "bj_merkle_nodes_d",
+                      "bj_hash_into_leaf_h", "bj_hash_into_node_h"),
+    "blake2s": _row("Blake2s256", "blake2::Blake2s256, cs/oracle/mod.rs:179-245",
+                    "bj_blake2s_leaves_d", "bj_blake2s_leaves_chunked_d", "bj_blake2s_nodes_d",
+                    "bj_blake2s_leaf_h", "bj_blake2s_node_h"),
+    "keccak256": _row("Keccak256", "sha3::Keccak256, cs/oracle/mod.rs:247-313",
+                      "bj_keccak256_leaves_d", "bj_keccak256_leaves_chunked_d", "bj_keccak256_nodes_d",
+                      "bj_keccak256_leaf_h", "bj_keccak256_node_h"),
 }
+Poseidon2Sponge, Blake2s256, Keccak256 = (HASHERS[k][0] for k in ("poseidon2", "blake2s", "keccak256"))
+
+
+def _poseidon2_permutation(state):
+    s = as_u64_host(state).copy()
+    if s.size != 12:
+        raise ValueError("state must have 12 elements")
+    call("bj_poseidon2_permute_h", _hp(s))
+    return s
+
+
+Poseidon2Sponge.poseidon2_permutation = staticmethod(_poseidon2_permutation)
 
 
 def _hasher(name):
@@ -146,7 +125,7 @@ class MerkleTreeWithCap:
 
     @classmethod
     def construct(cls, leafs_sources, cap_size, num_cosets=None, leaf_out=None, node_out=None, hasher="poseidon2"):
-        _, f_leaves, _, f_nodes = _hasher(hasher)
+        f_leaves, f_nodes = _hasher(hasher)[1], _hasher(hasher)[3]
         src, c, stride, nl = _leaf_sources(leafs_sources, num_cosets)
         _log2(nl)
         _log2(cap_size)
@@ -197,7 +176,7 @@ class MerkleTreeWithCap:
 
     @classmethod
     def _chunked(cls, src, c, stride, nl, e, cap_size, hasher):
-        _, _, f_chunked, f_nodes = _hasher(hasher)
+        f_chunked, f_nodes = _hasher(hasher)[2:4]
         _log2(nl)
         dev = src.device
         leaves = torch.empty((nl, 4), dtype=torch.int64, device=dev)

@@ -89,8 +89,6 @@ hipError_t launch_b2s_leaves(const uint64_t* src, size_t col_stride, uint32_t n_
                              hipStream_t st);
 hipError_t launch_b2s_leaves_chunked(const uint64_t* src, size_t col_stride, uint32_t n_cols, uint32_t log_e,
                                      size_t n_leaves, uint64_t* out, hipStream_t st);
-hipError_t launch_b2s_nodes(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes,
-                            hipStream_t st);
 hipError_t launch_b2s_words(const uint64_t* words, uint32_t n_words, uint64_t* out, hipStream_t st);
 
 // keccak.hip: Keccak256 tree hasher (cs/oracle/mod.rs:247-313)
@@ -98,8 +96,43 @@ hipError_t launch_kc_leaves(const uint64_t* src, size_t col_stride, uint32_t n_c
                             hipStream_t st);
 hipError_t launch_kc_leaves_chunked(const uint64_t* src, size_t col_stride, uint32_t n_cols, uint32_t log_e,
                                     size_t n_leaves, uint64_t* out, hipStream_t st);
-hipError_t launch_kc_nodes(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes,
-                           hipStream_t st);
+
+// tree_hasher.hpp: the node levels of hasher trait H, one node per lane and one grid per level
+// down to tail_from digests (at most NODE_TAIL_MAX, what the tail's LDS buffers hold), the rest
+// in the one-workgroup tail.  Instantiated in the hasher's own file (blake2s.hip, keccak.hip).
+constexpr size_t NODE_TAIL_MAX = 4096;
+struct B2sNode;
+struct KcNode;
+template <class H>
+hipError_t launch_nodes_per_lane(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes,
+                                 size_t tail_from, hipStream_t st);
+
+// capi_tree.hip: what the host side needs of a tree hasher, one row per BJ_HASHER_*
+struct TreeOps {
+    // leaf L = src[c][L], c < n_cols, continuing a leaf of which cols_before columns went before
+    // (their carried state in state_in, NULL for the first range); final_: out receives the
+    // digests, otherwise the state to carry on
+    hipError_t (*leaves)(const uint64_t* src, size_t col_stride, uint32_t n_cols, size_t n_leaves,
+                         uint64_t cols_before, const uint64_t* state_in, uint64_t* out, bool final_, hipStream_t st);
+    hipError_t (*leaves_chunked)(const uint64_t* src, size_t col_stride, uint32_t n_cols, uint32_t log_e,
+                                 size_t n_leaves, uint64_t* out, hipStream_t st);
+    hipError_t (*nodes)(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes, hipStream_t st);
+    // one leaf of n_words contiguous elements (the *_leaf_h seams)
+    hipError_t (*message)(const uint64_t* words, uint32_t n_words, uint64_t* out4, hipStream_t st);
+    bool continues;  // a leaf can be absorbed over several column ranges (leaves with final_ false)
+};
+// NULL for a hasher outside BJ_HASHER_*
+const TreeOps* tree_ops(int hasher);
+// The argument checks of the tree entry points (BJ_EINVAL with the reference's wording), then the
+// hasher's launch; `hasher` is a valid BJ_HASHER_*.
+int tree_nodes(int hasher, const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes,
+               hipStream_t st);
+int tree_leaves_chunked(int hasher, const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves,
+                        uint32_t elems_per_leaf, uint64_t* out, hipStream_t st);
+int tree_leaves_partial(int hasher, const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves,
+                        uint64_t cols_before, const uint64_t* state_in, uint64_t* out, bool final_, hipStream_t st);
+int tree_node_h(int hasher, const uint64_t* left4, const uint64_t* right4, uint64_t* out4);
+int tree_leaf_h(int hasher, const uint64_t* elems, size_t n_elems, uint64_t* out4);
 
 // shard.hip: sub-coset fold of the bit-reversed coefficients (G > D shards)
 constexpr uint32_t kMaxFold = 64;

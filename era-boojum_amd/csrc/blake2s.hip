@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "gl.hpp"
 #include "bj_internal.hpp"
+#include "tree_hasher.hpp"
 
 namespace bj {
 
@@ -188,66 +189,6 @@ __global__ __launch_bounds__(B2S_THREADS) void b2s_leaf_chunk_kernel(const uint6
     store_digest(h, out + 4 * L);
 }
 
-__device__ __forceinline__ void node_hash(const uint64_t* l, const uint64_t* r, uint64_t* o) {
-    uint32_t h[8], m[16];
-    init_h(h);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        m[2 * i] = (uint32_t)l[i];
-        m[2 * i + 1] = (uint32_t)(l[i] >> 32);
-        m[8 + 2 * i] = (uint32_t)r[i];
-        m[8 + 2 * i + 1] = (uint32_t)(r[i] >> 32);
-    }
-    compress(h, m, 64, 0, true);
-    store_digest(h, o);
-}
-
-__global__ __launch_bounds__(256) void b2s_node_level_kernel(const uint64_t* __restrict__ prev,
-                                                             uint64_t* __restrict__ next, size_t m) {
-    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
-    if (i >= m) return;
-    uint64_t lr[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) lr[k] = prev[8 * i + k];
-    node_hash(lr, lr + 4, next + 4 * i);
-}
-
-// Remaining levels from `len` digests (len <= 4096) down to cap_size, one workgroup.
-__global__ __launch_bounds__(256) void b2s_node_tail_kernel(const uint64_t* __restrict__ prev, uint64_t* next,
-                                                            uint32_t len, uint32_t cap_size) {
-    __shared__ uint64_t buf[2][2048 * 4];
-    int cur = 0;
-    uint64_t* outp = next;
-    uint32_t m = len / 2;
-    for (uint32_t i = threadIdx.x; i < m; i += 256) {
-        uint64_t lr[8];
-        for (int k = 0; k < 8; k++) lr[k] = prev[8 * (size_t)i + k];
-        uint64_t o[4];
-        node_hash(lr, lr + 4, o);
-        for (int k = 0; k < 4; k++) {
-            buf[cur][4 * i + k] = o[k];
-            outp[4 * (size_t)i + k] = o[k];
-        }
-    }
-    outp += 4 * (size_t)m;
-    __syncthreads();
-    while (m > cap_size) {
-        const uint32_t m2 = m / 2;
-        for (uint32_t i = threadIdx.x; i < m2; i += 256) {
-            uint64_t o[4];
-            node_hash(&buf[cur][8 * i], &buf[cur][8 * i + 4], o);
-            for (int k = 0; k < 4; k++) {
-                buf[cur ^ 1][4 * i + k] = o[k];
-                outp[4 * (size_t)i + k] = o[k];
-            }
-        }
-        outp += 4 * (size_t)m2;
-        cur ^= 1;
-        m = m2;
-        __syncthreads();
-    }
-}
-
 // one whole message per lane (the host seam bj_blake2s_leaf_h and its tests)
 __global__ void b2s_bytes_kernel(const uint64_t* __restrict__ words, uint32_t n_words, uint64_t* out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -266,6 +207,24 @@ __global__ void b2s_bytes_kernel(const uint64_t* __restrict__ words, uint32_t n_
 }
 
 }  // namespace
+
+// hash_into_node: one final block, left || right; the node levels are tree_hasher.hpp's
+struct B2sNode {
+    static __device__ __forceinline__ void node(const uint64_t* l, const uint64_t* r, uint64_t* o) {
+        uint32_t h[8], m[16];
+        init_h(h);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            m[2 * i] = (uint32_t)l[i];
+            m[2 * i + 1] = (uint32_t)(l[i] >> 32);
+            m[8 + 2 * i] = (uint32_t)r[i];
+            m[8 + 2 * i + 1] = (uint32_t)(r[i] >> 32);
+        }
+        compress(h, m, 64, 0, true);
+        store_digest(h, o);
+    }
+};
+template hipError_t launch_nodes_per_lane<B2sNode>(const uint64_t*, size_t, uint32_t, uint64_t*, size_t, hipStream_t);
 
 hipError_t launch_b2s_leaves(const uint64_t* src, size_t col_stride, uint32_t n_cols, size_t n_leaves,
                              uint64_t cols_before, const uint64_t* state_in, uint64_t* out, bool final_,
@@ -291,23 +250,6 @@ hipError_t launch_b2s_leaves_chunked(const uint64_t* src, size_t col_stride, uin
     if (n_leaves == 0) return hipSuccess;
     hipLaunchKernelGGL(b2s_leaf_chunk_kernel, dim3((unsigned)((n_leaves + B2S_THREADS - 1) / B2S_THREADS)),
                        dim3(B2S_THREADS), 0, st, src, col_stride, n_cols, log_e, n_leaves, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_b2s_nodes(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes,
-                            hipStream_t st) {
-    const uint64_t* prev = leaves;
-    uint64_t* out = nodes;
-    size_t len = n_leaves;
-    while (len > cap_size && len > 4096) {
-        const size_t m = len / 2;
-        hipLaunchKernelGGL(b2s_node_level_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, prev, out, m);
-        prev = out;
-        out += 4 * m;
-        len = m;
-    }
-    if (len > cap_size)
-        hipLaunchKernelGGL(b2s_node_tail_kernel, dim3(1), dim3(256), 0, st, prev, out, (uint32_t)len, cap_size);
     return hipGetLastError();
 }
 

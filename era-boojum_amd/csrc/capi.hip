@@ -14,30 +14,15 @@
 #include <thread>
 #include <condition_variable>
 
-#include "../../include/boojum_mi355x.h"
 #include "gl.hpp"
-#include "bj_internal.hpp"
+#include "capi_common.hpp"
+
+using namespace bj::capi;
 
 namespace {
 
+// the library's one bj_last_error() string per thread; every file writes it through bj::set_error
 thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-    return fail(BJ_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(expr, what)                       \
-    do {                                          \
-        hipError_t _e = (expr);                   \
-        if (_e != hipSuccess) return hip_fail(_e, what); \
-    } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ------------------------------------------------------------ device cache
 // Twiddle, power and LDE factor tables per device and size.  Entries are computed
@@ -219,8 +204,6 @@ int get_lde3_lde(uint32_t log_n, uint32_t log_d, const uint64_t** out) {
 // same-binary A/B measurements.
 bool use_lde3(uint32_t log_n) { return bj::knobs().lde_passes != 2 && bj::lde3_supported(log_n); }
 
-inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
-
 int log2_exact(size_t len, uint32_t* out) {
     if (!is_pow2(len)) return fail(BJ_EINVAL, "length must be a power of two");
     uint32_t l = 0;
@@ -239,33 +222,6 @@ uint64_t lde_coset(uint32_t log_n, uint32_t log_d, uint32_t i) {
     uint64_t g = gl::domain_generator(log_n + log_d);
     return gl::canon(gl::mul(gl::pow(g, gl::bitrev32(i, log_d)), gl::GENERATOR));
 }
-
-// The *_h entry points run on a stream of their own per calling thread and device (created
-// once; stream creation costs milliseconds on ROCm), with stream-ordered device buffers and
-// explicit copies + synchronisation.  Nothing of theirs touches the legacy null stream, which
-// every host thread shares.
-int seam_stream(hipStream_t* out) {
-    thread_local std::map<int, hipStream_t> tl;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev), "hipGetDevice");
-    auto it = tl.find(dev);
-    if (it == tl.end()) {
-        hipStream_t st;
-        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-        it = tl.emplace(dev, st).first;
-    }
-    *out = it->second;
-    return BJ_OK;
-}
-
-// Stream-ordered device buffer RAII for the *_h entry points.
-struct DBuf {
-    uint64_t* p = nullptr;
-    hipStream_t st = nullptr;
-    explicit DBuf(hipStream_t s) : st(s) {}
-    hipError_t alloc(size_t bytes) { return bj::pool_alloc((void**)&p, bytes, st); }
-    ~DBuf() { if (p) (void)hipFreeAsync(p, st); }
-};
 
 }  // namespace
 
@@ -374,7 +330,10 @@ int shard_from_folded(const uint64_t* folded, size_t folded_stride, uint32_t n_c
 }  // namespace
 
 namespace bj {
-int set_error(int code, const char* msg) { return fail(code, msg); }
+int set_error(int code, const char* msg) {
+    g_err = msg;
+    return code;
+}
 
 bool lde_fused_supported(uint32_t log_n) { return use_lde3(log_n); }
 
@@ -777,112 +736,6 @@ int bj_gl_op_d(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size
     return BJ_OK;
 }
 
-int bj_poseidon2_permute_d(uint64_t* states, size_t count, void* stream) {
-    HIP_TRY(bj::launch_permute(states, count, S(stream)), "permute");
-    return BJ_OK;
-}
-
-int bj_merkle_leaves_d(const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves, uint64_t* leaves,
-                       void* stream) {
-    HIP_TRY(bj::launch_leaves(src, col_stride, n_cols, n_leaves, leaves, S(stream)), "leaves");
-    return BJ_OK;
-}
-
-int bj_merkle_leaves_partial_d(const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves,
-                               const uint64_t* cap_in, uint64_t* out, int final_, void* stream) {
-    if (!final_ && (n_cols & 7))
-        return fail(BJ_EINVAL, "a non-final column range must be a multiple of the sponge rate (8)");
-    if (final_ && cap_in && n_cols == 0)
-        return fail(BJ_EINVAL, "the final column range of a continued sponge must be non-empty");
-    HIP_TRY(bj::launch_leaves_partial(src, col_stride, n_cols, n_leaves, cap_in, out, final_ != 0, S(stream)),
-            "leaves");
-    return BJ_OK;
-}
-
-int bj_merkle_leaves_chunked_d(const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves,
-                               uint32_t elems_per_leaf, uint64_t* out, void* stream) {
-    if (!is_pow2(elems_per_leaf)) return fail(BJ_EINVAL, "elements_to_take_per_leaf must be a power of two");
-    uint32_t log_e = 0;
-    while ((1u << log_e) < elems_per_leaf) log_e++;
-    if ((uint64_t)n_cols << log_e > 0xFFFFFFFFull) return fail(BJ_EINVAL, "leaf too long");
-    HIP_TRY(bj::launch_leaves_chunked(src, col_stride, n_cols, log_e, n_leaves, out, S(stream)), "leaves");
-    return BJ_OK;
-}
-
-int bj_merkle_nodes_d(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes, void* stream) {
-    if (!is_pow2(n_leaves) || !is_pow2(cap_size) || n_leaves <= cap_size)
-        return fail(BJ_EINVAL, "need power-of-two n_leaves > cap_size (merkle_tree.rs:83-96)");
-    HIP_TRY(bj::launch_nodes(leaves, n_leaves, cap_size, nodes, S(stream)), "nodes");
-    return BJ_OK;
-}
-
-// ------------------------------------------------------------ Blake2s256 trees
-
-int bj_blake2s_leaves_d(const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves, uint64_t* leaves,
-                        void* stream) {
-    HIP_TRY(bj::launch_b2s_leaves(src, col_stride, n_cols, n_leaves, 0, nullptr, leaves, true, S(stream)), "leaves");
-    return BJ_OK;
-}
-
-int bj_blake2s_leaves_partial_d(const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves,
-                                uint64_t cols_before, const uint64_t* state_in, uint64_t* out, int final_,
-                                void* stream) {
-    if (cols_before & 7) return fail(BJ_EINVAL, "cols_before must be a multiple of the block (8 elements)");
-    if ((cols_before != 0) != (state_in != nullptr))
-        return fail(BJ_EINVAL, "state_in is required exactly when cols_before > 0");
-    if (!final_ && (n_cols & 7))
-        return fail(BJ_EINVAL, "a non-final column range must be a multiple of the block (8 elements)");
-    if (final_ && cols_before && n_cols == 0)
-        return fail(BJ_EINVAL, "the final column range of a continued message must be non-empty");
-    HIP_TRY(bj::launch_b2s_leaves(src, col_stride, n_cols, n_leaves, cols_before, state_in, out, final_ != 0,
-                                  S(stream)),
-            "leaves");
-    return BJ_OK;
-}
-
-int bj_blake2s_leaves_chunked_d(const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves,
-                                uint32_t elems_per_leaf, uint64_t* out, void* stream) {
-    if (!is_pow2(elems_per_leaf)) return fail(BJ_EINVAL, "elements_to_take_per_leaf must be a power of two");
-    uint32_t log_e = 0;
-    while ((1u << log_e) < elems_per_leaf) log_e++;
-    if ((uint64_t)n_cols << log_e > 0xFFFFFFFFull) return fail(BJ_EINVAL, "leaf too long");
-    HIP_TRY(bj::launch_b2s_leaves_chunked(src, col_stride, n_cols, log_e, n_leaves, out, S(stream)), "leaves");
-    return BJ_OK;
-}
-
-int bj_blake2s_nodes_d(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes, void* stream) {
-    if (!is_pow2(n_leaves) || !is_pow2(cap_size) || n_leaves <= cap_size)
-        return fail(BJ_EINVAL, "need power-of-two n_leaves > cap_size (merkle_tree.rs:83-96)");
-    HIP_TRY(bj::launch_b2s_nodes(leaves, n_leaves, cap_size, nodes, S(stream)), "nodes");
-    return BJ_OK;
-}
-
-// ------------------------------------------------------------ Keccak256 trees
-
-int bj_keccak256_leaves_d(const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves, uint64_t* leaves,
-                          void* stream) {
-    HIP_TRY(bj::launch_kc_leaves(src, col_stride, n_cols, n_leaves, leaves, S(stream)), "leaves");
-    return BJ_OK;
-}
-
-int bj_keccak256_leaves_chunked_d(const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves,
-                                  uint32_t elems_per_leaf, uint64_t* out, void* stream) {
-    if (!is_pow2(elems_per_leaf)) return fail(BJ_EINVAL, "elements_to_take_per_leaf must be a power of two");
-    uint32_t log_e = 0;
-    while ((1u << log_e) < elems_per_leaf) log_e++;
-    if ((uint64_t)n_cols << log_e > 0xFFFFFFFFull) return fail(BJ_EINVAL, "leaf too long");
-    HIP_TRY(bj::launch_kc_leaves_chunked(src, col_stride, n_cols, log_e, n_leaves, out, S(stream)), "leaves");
-    return BJ_OK;
-}
-
-int bj_keccak256_nodes_d(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes,
-                         void* stream) {
-    if (!is_pow2(n_leaves) || !is_pow2(cap_size) || n_leaves <= cap_size)
-        return fail(BJ_EINVAL, "need power-of-two n_leaves > cap_size (merkle_tree.rs:83-96)");
-    HIP_TRY(bj::launch_kc_nodes(leaves, n_leaves, cap_size, nodes, S(stream)), "nodes");
-    return BJ_OK;
-}
-
 namespace {
 int commit_d(const uint64_t* trace, uint32_t n_cols, size_t trace_stride, uint32_t log_n, uint32_t log_lde,
              uint32_t log_commit_cosets, uint32_t cap_size, uint64_t* scratch, uint64_t* lde, uint64_t* leaves,
@@ -936,13 +789,6 @@ int bj_lde_commit_ex_d(const uint64_t* trace, uint32_t n_cols, size_t trace_stri
 
 // --------------------------------------------------------- host-pointer seam
 
-#define SEAM_BEGIN            \
-    hipStream_t st;           \
-    if (int r_ = seam_stream(&st)) return r_
-#define H2D(dst, src, bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "memcpy")
-#define D2H(dst, src, bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "memcpy")
-#define SEAM_END HIP_TRY(hipStreamSynchronize(st), "sync")
-
 int bj_distribute_powers_h(uint64_t* col, size_t len, uint64_t element) {
     uint32_t log_n;
     if (int r = log2_exact(len, &log_n)) return r;
@@ -978,92 +824,6 @@ int bj_ifft_natural_to_natural_h(uint64_t* col, size_t len, uint64_t coset) {
     H2D(d.p, col, len * 8);
     if (int r = bj_ifft_natural_to_natural_d(d.p, 1, len, log_n, coset, nullptr, st)) return r;
     D2H(col, d.p, len * 8);
-    SEAM_END;
-    return BJ_OK;
-}
-
-int bj_poseidon2_permute_h(uint64_t* state12) {
-    SEAM_BEGIN;
-    DBuf d(st);
-    HIP_TRY(d.alloc(96), "hipMallocAsync");
-    H2D(d.p, state12, 96);
-    if (int r = bj_poseidon2_permute_d(d.p, 1, st)) return r;
-    D2H(state12, d.p, 96);
-    SEAM_END;
-    return BJ_OK;
-}
-
-int bj_hash_into_leaf_h(const uint64_t* elems, size_t n_elems, uint64_t* out4) {
-    SEAM_BEGIN;
-    DBuf d(st), o(st);
-    HIP_TRY(d.alloc(n_elems * 8), "hipMallocAsync");
-    HIP_TRY(o.alloc(32), "hipMallocAsync");
-    if (n_elems) H2D(d.p, elems, n_elems * 8);
-    if (int r = bj_merkle_leaves_d(d.p, (uint32_t)n_elems, 1, 1, o.p, st)) return r;
-    D2H(out4, o.p, 32);
-    SEAM_END;
-    return BJ_OK;
-}
-
-int bj_hash_into_node_h(const uint64_t* left4, const uint64_t* right4, uint64_t* out4) {
-    SEAM_BEGIN;
-    DBuf d(st);
-    HIP_TRY(d.alloc(96), "hipMallocAsync");
-    H2D(d.p, left4, 32);
-    H2D(d.p + 4, right4, 32);
-    if (int r = bj_merkle_nodes_d(d.p, 2, 1, d.p + 8, st)) return r;
-    D2H(out4, d.p + 8, 32);
-    SEAM_END;
-    return BJ_OK;
-}
-
-int bj_blake2s_leaf_h(const uint64_t* elems, size_t n_elems, uint64_t* out4) {
-    if (n_elems > 0xFFFFFFFFull) return fail(BJ_EINVAL, "leaf too long");
-    SEAM_BEGIN;
-    DBuf d(st), o(st);
-    HIP_TRY(d.alloc(n_elems * 8), "hipMallocAsync");
-    HIP_TRY(o.alloc(32), "hipMallocAsync");
-    if (n_elems) H2D(d.p, elems, n_elems * 8);
-    HIP_TRY(bj::launch_b2s_words(d.p, (uint32_t)n_elems, o.p, st), "blake2s");
-    D2H(out4, o.p, 32);
-    SEAM_END;
-    return BJ_OK;
-}
-
-int bj_blake2s_node_h(const uint64_t* left4, const uint64_t* right4, uint64_t* out4) {
-    SEAM_BEGIN;
-    DBuf d(st);
-    HIP_TRY(d.alloc(96), "hipMallocAsync");
-    H2D(d.p, left4, 32);
-    H2D(d.p + 4, right4, 32);
-    if (int r = bj_blake2s_nodes_d(d.p, 2, 1, d.p + 8, st)) return r;
-    D2H(out4, d.p + 8, 32);
-    SEAM_END;
-    return BJ_OK;
-}
-
-int bj_keccak256_leaf_h(const uint64_t* elems, size_t n_elems, uint64_t* out4) {
-    if (n_elems > 0xFFFFFFFFull) return fail(BJ_EINVAL, "leaf too long");
-    SEAM_BEGIN;
-    DBuf d(st), o(st);
-    HIP_TRY(d.alloc(n_elems * 8), "hipMallocAsync");
-    HIP_TRY(o.alloc(32), "hipMallocAsync");
-    if (n_elems) H2D(d.p, elems, n_elems * 8);
-    // the elements as n_elems one-row columns of one leaf
-    HIP_TRY(bj::launch_kc_leaves(d.p, 1, (uint32_t)n_elems, 1, o.p, st), "keccak256");
-    D2H(out4, o.p, 32);
-    SEAM_END;
-    return BJ_OK;
-}
-
-int bj_keccak256_node_h(const uint64_t* left4, const uint64_t* right4, uint64_t* out4) {
-    SEAM_BEGIN;
-    DBuf d(st);
-    HIP_TRY(d.alloc(96), "hipMallocAsync");
-    H2D(d.p, left4, 32);
-    H2D(d.p + 4, right4, 32);
-    if (int r = bj_keccak256_nodes_d(d.p, 2, 1, d.p + 8, st)) return r;
-    D2H(out4, d.p + 8, 32);
     SEAM_END;
     return BJ_OK;
 }

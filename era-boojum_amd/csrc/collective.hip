@@ -370,9 +370,8 @@ std::vector<Run> column_runs(uint32_t n_cols, uint32_t world, uint32_t rank, int
         w = t;
     }
     const uint32_t unit = 8 / gcd;
-    const bool partial = hasher == BJ_HASHER_POSEIDON2 || hasher == BJ_HASHER_BLAKE2S;
     std::vector<Run> runs;
-    if (world == 1 || cpr % unit != 0 || !partial) {
+    if (world == 1 || cpr % unit != 0 || !bj::tree_ops(hasher)->continues) {
         runs.push_back({0, rank * cpr, cpr, 0, n_cols});
         return runs;
     }
@@ -447,13 +446,7 @@ struct XsJoin {
     }
 };
 
-int nodes_for(int hasher, const uint64_t* leaves, size_t n, uint32_t cap, uint64_t* nodes, void* st) {
-    switch (hasher) {
-        case BJ_HASHER_POSEIDON2: return bj_merkle_nodes_d(leaves, n, cap, nodes, st);
-        case BJ_HASHER_BLAKE2S: return bj_blake2s_nodes_d(leaves, n, cap, nodes, st);
-        default: return bj_keccak256_nodes_d(leaves, n, cap, nodes, st);
-    }
-}
+int check_hasher(int hasher) { return bj::tree_ops(hasher) ? BJ_OK : err(BJ_EINVAL, "unknown hasher"); }
 
 }  // namespace
 
@@ -721,7 +714,7 @@ int bj_sharded_columns(uint32_t n_cols, uint32_t log_shards, uint32_t shard, int
     const uint32_t world = 1u << log_shards;
     if (!cols_out || shard >= world || n_cols % world)
         return err(BJ_EINVAL, "need n_cols a multiple of the shard count and shard < G");
-    if (hasher < BJ_HASHER_POSEIDON2 || hasher > BJ_HASHER_KECCAK256) return err(BJ_EINVAL, "unknown hasher");
+    BJ_CHECK(check_hasher(hasher));
     size_t j = 0;
     for (const Run& r : column_runs(n_cols, world, shard, hasher))
         for (uint32_t i = 0; i < r.count; i++) cols_out[j++] = r.global + i;
@@ -733,7 +726,7 @@ int bj_sharded_commit_d(bj_comm* comm, const uint64_t* trace_shard, size_t trace
                         uint64_t* lde, uint64_t* leaves, uint64_t* nodes, uint64_t* cap, void* stream) {
     if (!comm) return err(BJ_EINVAL, "null communicator");
     GroupAbort abort_guard(comm);
-    if (hasher < BJ_HASHER_POSEIDON2 || hasher > BJ_HASHER_KECCAK256) return err(BJ_EINVAL, "unknown hasher");
+    BJ_CHECK(check_hasher(hasher));
     const uint32_t world = (uint32_t)comm->world, rank = (uint32_t)comm->rank;
     const uint32_t log_g = log2u(world), log_k = log_commit_cosets;
     if (n_cols == 0 || n_cols % world) return err(BJ_EINVAL, "n_cols must be a positive multiple of the world size");
@@ -858,12 +851,7 @@ int bj_sharded_commit_d(bj_comm* comm, const uint64_t* trace_shard, size_t trace
         const uint64_t* cin = k0 == 0 ? nullptr : state;
         uint64_t* dst = last ? leaves : state;
         BJ_CHECK(pt.begin(2));
-        if (hasher == BJ_HASHER_POSEIDON2)
-            BJ_CHECK(bj_merkle_leaves_partial_d(out, cc, m, m, cin, dst, last ? 1 : 0, st));
-        else if (hasher == BJ_HASHER_BLAKE2S)
-            BJ_CHECK(bj_blake2s_leaves_partial_d(out, cc, m, m, c0, cin, dst, last ? 1 : 0, st));
-        else
-            BJ_CHECK(bj_keccak256_leaves_d(out, cc, m, m, dst, st));
+        BJ_CHECK(bj::tree_leaves_partial(hasher, out, cc, m, m, c0, cin, dst, last, st));
         return pt.end();
     };
     // chunk k's leaves follow chunk k + defer's LDE (leaves_defer(), 0 in production), `group`
@@ -922,7 +910,7 @@ int bj_sharded_commit_d(bj_comm* comm, const uint64_t* trace_shard, size_t trace
     BJ_CHECK(absorb_ready(K, true));
     // 3. this rank's subtree, then the cap
     BJ_CHECK(pt.begin(3));
-    BJ_CHECK(nodes_for(hasher, leaves, m, cap_local, nodes, st));
+    BJ_CHECK(bj::tree_nodes(hasher, leaves, m, cap_local, nodes, st));
     BJ_CHECK(pt.end());
     const uint64_t* local_cap = nodes + (m - 2 * (size_t)cap_local) * 4;
     if (cap_size >= world) {
@@ -933,7 +921,7 @@ int bj_sharded_commit_d(bj_comm* comm, const uint64_t* trace_shard, size_t trace
         HIP_CHECK(ws.alloc(&roots, (size_t)world * 4), "pool_alloc");
         HIP_CHECK(ws.alloc(&top, (size_t)(world - cap_size) * 4), "pool_alloc");
         BJ_CHECK(all_gather(comm, local_cap, roots, 32, st));
-        BJ_CHECK(nodes_for(hasher, roots, world, cap_size, top, st));
+        BJ_CHECK(bj::tree_nodes(hasher, roots, world, cap_size, top, st));
         HIP_CHECK(hipMemcpyAsync(cap, top + (size_t)(world - 2 * cap_size) * 4, (size_t)cap_size * 32,
                                  hipMemcpyDeviceToDevice, st),
                   "memcpy cap");
@@ -949,7 +937,7 @@ int bj_sharded_query_h(bj_comm* comm, const uint64_t* lde, const uint64_t* leave
                        void* stream) {
     if (!comm) return err(BJ_EINVAL, "null communicator");
     GroupAbort abort_guard(comm);
-    if (hasher < BJ_HASHER_POSEIDON2 || hasher > BJ_HASHER_KECCAK256) return err(BJ_EINVAL, "unknown hasher");
+    BJ_CHECK(check_hasher(hasher));
     const uint32_t world = (uint32_t)comm->world, rank = (uint32_t)comm->rank;
     const uint32_t log_g = log2u(world);
     if (log_commit_cosets > log_lde) return err(BJ_EINVAL, "committed cosets exceed the lde degree");
@@ -993,7 +981,7 @@ int bj_sharded_query_h(bj_comm* comm, const uint64_t* lde, const uint64_t* leave
         HIP_CHECK(ws.alloc(&roots, (size_t)world * 4), "pool_alloc");
         HIP_CHECK(ws.alloc(&top, (size_t)(world - cap_size) * 4), "pool_alloc");
         BJ_CHECK(all_gather(comm, nodes + (m - 2 * (size_t)cap_local) * 4, roots, 32, st));
-        BJ_CHECK(nodes_for(hasher, roots, world, cap_size, top, st));
+        BJ_CHECK(bj::tree_nodes(hasher, roots, world, cap_size, top, st));
         size_t at = owner, level_off = 0, level_len = world;
         for (uint32_t l = 0; l < top_depth; l++) {
             const uint64_t* src = l == 0 ? roots + 4 * (at ^ 1) : top + 4 * (level_off + (at ^ 1));

@@ -15,6 +15,7 @@
 #include "poseidon2.hpp"
 #include "poseidon2_quad.hpp"
 #include "bj_internal.hpp"
+#include "tree_hasher.hpp"
 
 namespace bj {
 
@@ -167,29 +168,22 @@ __global__ __launch_bounds__(LEAF_THREADS) void leaf_chunk_kernel(const uint64_t
     store_canon4(s, out + 4 * L);
 }
 
-__device__ __forceinline__ void node_hash(const uint64_t* l, const uint64_t* r, uint64_t* o) {
-    p2::State s;
+// hash_into_node, one lane; the per-lane levels and the one-workgroup tail are tree_hasher.hpp's
+struct P2Node {
+    static __device__ __forceinline__ void node(const uint64_t* l, const uint64_t* r, uint64_t* o) {
+        p2::State s;
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        s.lo[i] = (uint32_t)l[i];
-        s.hi[i] = (uint32_t)(l[i] >> 32);
-        s.lo[4 + i] = (uint32_t)r[i];
-        s.hi[4 + i] = (uint32_t)(r[i] >> 32);
-        s.lo[8 + i] = s.hi[8 + i] = 0;
+        for (int i = 0; i < 4; i++) {
+            s.lo[i] = (uint32_t)l[i];
+            s.hi[i] = (uint32_t)(l[i] >> 32);
+            s.lo[4 + i] = (uint32_t)r[i];
+            s.hi[4 + i] = (uint32_t)(r[i] >> 32);
+            s.lo[8 + i] = s.hi[8 + i] = 0;
+        }
+        p2::permute<p2::OUT_DIGEST>(s);
+        store_canon4(s, o);
     }
-    p2::permute<p2::OUT_DIGEST>(s);
-    store_canon4(s, o);
-}
-
-__global__ __launch_bounds__(256) void node_level_kernel(const uint64_t* __restrict__ prev,
-                                                         uint64_t* __restrict__ next, size_t m) {
-    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
-    if (i >= m) return;
-    uint64_t lr[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) lr[k] = prev[8 * i + k];
-    node_hash(lr, lr + 4, next + 4 * i);
-}
+};
 
 // One node per quad of lanes (poseidon2_quad.hpp): for the levels too small to fill the chip,
 // where a level costs one permutation's latency and the quad form shortens it ~2.5x.
@@ -265,37 +259,6 @@ __global__ __launch_bounds__(NODE_FUSED_THREADS) void node_levels_q4_kernel(cons
     }
 }
 
-// Remaining levels from `len` digests (len <= 4096; launch_nodes hands over len <= 512) down to
-// cap_size, one workgroup.
-__global__ __launch_bounds__(256) void node_tail_kernel(const uint64_t* __restrict__ prev, uint64_t* next,
-                                                        uint32_t len, uint32_t cap_size) {
-    __shared__ uint64_t buf[2][2048 * 4];
-    int cur = 0;
-    uint64_t* outp = next;
-    uint32_t m = len / 2;
-    for (uint32_t i = threadIdx.x; i < m; i += 256) {
-        uint64_t lr[8];
-        for (int k = 0; k < 8; k++) lr[k] = prev[8 * (size_t)i + k];
-        uint64_t o[4];
-        node_hash(lr, lr + 4, o);
-        for (int k = 0; k < 4; k++) { buf[cur][4 * i + k] = o[k]; outp[4 * (size_t)i + k] = o[k]; }
-    }
-    outp += 4 * (size_t)m;
-    __syncthreads();
-    while (m > cap_size) {
-        uint32_t m2 = m / 2;
-        for (uint32_t i = threadIdx.x; i < m2; i += 256) {
-            uint64_t o[4];
-            node_hash(&buf[cur][8 * i], &buf[cur][8 * i + 4], o);
-            for (int k = 0; k < 4; k++) { buf[cur ^ 1][4 * i + k] = o[k]; outp[4 * (size_t)i + k] = o[k]; }
-        }
-        outp += 4 * (size_t)m2;
-        cur ^= 1;
-        m = m2;
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(256) void permute_kernel(uint64_t* states, size_t count) {
     const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
     if (i >= count) return;
@@ -354,9 +317,6 @@ static size_t node_q4_max() { return (size_t)knobs().node_q4_max; }
 
 hipError_t launch_nodes(const uint64_t* leaves, size_t n_leaves, uint32_t cap_size, uint64_t* nodes,
                         hipStream_t st) {
-    const uint64_t* prev = leaves;
-    uint64_t* out = nodes;
-    size_t len = n_leaves;
     // every level above 512 digests as its own grid: a level costs one permutation's latency
     // (~20 us at one wave per SIMD) when every lane hashes one node, while one workgroup
     // would run a 2048-node level as 8 permutations in sequence.  Levels of <= q4max nodes
@@ -364,9 +324,13 @@ hipError_t launch_nodes(const uint64_t* leaves, size_t n_leaves, uint32_t cap_si
     // own grid down to the cap; BJ_NODE_Q4_MAX=0 keeps one node per lane and the one-workgroup
     // tail for the last levels.
     const size_t q4max = node_q4_max();
+    if (!q4max) return launch_nodes_per_lane<P2Node>(leaves, n_leaves, cap_size, nodes, 512, st);
+    const uint64_t* prev = leaves;
+    uint64_t* out = nodes;
+    size_t len = n_leaves;
     const auto pow2 = [](size_t x) { return x && !(x & (x - 1)); };
     const bool fuse = knobs().node_fused && pow2(n_leaves) && pow2(cap_size);
-    while (len > cap_size && (q4max || len > 512)) {
+    while (len > cap_size) {
         size_t m = len / 2;
         if (m <= q4max && fuse) {
             // up to 8 levels per launch (node_levels_q4_kernel): blocks of 2^b digests
@@ -384,13 +348,11 @@ hipError_t launch_nodes(const uint64_t* leaves, size_t n_leaves, uint32_t cap_si
         if (m <= q4max)
             hipLaunchKernelGGL(node_level_q4_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, st, prev, out, m);
         else
-            hipLaunchKernelGGL(node_level_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, prev, out, m);
+            hipLaunchKernelGGL(node_level_kernel<P2Node>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, prev,
+                               out, m);
         prev = out;
         out += 4 * m;
         len = m;
-    }
-    if (len > cap_size) {
-        hipLaunchKernelGGL(node_tail_kernel, dim3(1), dim3(256), 0, st, prev, out, (uint32_t)len, cap_size);
     }
     return hipGetLastError();
 }

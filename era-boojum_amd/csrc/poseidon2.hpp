@@ -73,7 +73,7 @@ constexpr int SH[12] = {4, 14, 11, 8, 0, 5, 2, 9, 13, 6, 3, 12};
 // whenever c < 2^64 - 2^41.
 constexpr uint64_t FULL_RC_BOUND = ~0ull - (1ull << 41) + 1;
 // After the last partial round L < 2^60.1 and H < 2^61.1 (mi_layer_b_limbs on mi_layer_a_g's limbs,
-// tests/test_poseidon2_sched.py::test_partial_pair_limb_bounds), so W = Hhi EPS + L + c < 2^64
+// tests/test_mi_layers_asm.py::test_partial_pair_limb_bounds), so W = Hhi EPS + L + c < 2^64
 // whenever c < 2^64 - 2^62; larger entries of rc26 go in as 32-bit limbs.
 constexpr uint64_t LIMB_RC_BOUND = (1ull << 63) + (1ull << 62);
 struct Values {
