@@ -13,8 +13,11 @@ package is the host-side mirror of the reference's interface for that path:
   sharded  multi-GPU commit (one process per GPU)
   deep     precompute_for_barycentric_evaluation_in_extension, barycentric_evaluate_*,
            quotening_operation_in_extension                  (utils.rs:907-1200, prover.rs:1501-2050, 2523-2706)
+  stage2   compute_partial_products_in_extension, compute_lookup_poly_pairs_specialized,
+           second_stage_trace                                (copy_permutation.rs:649-774,
+                                                              lookup_argument_in_ext.rs:320-700, prover.rs:360-438)
 """
 from ._lib import BoojumError, load  # noqa: F401
 from .field import P, GENERATOR  # noqa: F401
 
-__all__ = ["fft", "lde", "merkle", "commit", "deep", "field", "BoojumError", "load", "P", "GENERATOR"]
+__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "field", "BoojumError", "load", "P", "GENERATOR"]

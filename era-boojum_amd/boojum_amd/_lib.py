@@ -88,6 +88,10 @@ SIGNATURES = {
     "bj_barycentric_weights_d": ([_u32, _u64, _u64, _u64, _vp, _vp, _vp], _int),
     "bj_evaluate_at_d": ([_vp, _u32, _sz, _u32, _vp, _vp, _vp, _vp], _int),
     "bj_deep_quotient_d": ([_vp, _u32, _sz, _vp, _u64, _u64, _u64, _u64, _u32, _sz, _sz, _vp, _vp, _int, _vp], _int),
+    "bj_copy_permutation_d": ([_vp, _sz, _vp, _sz, _u32, _u32, _u64p, _u64, _u64, _u64, _u64, _u32, _vp, _sz, _vp,
+                               _vp], _int),
+    "bj_lookup_encoding_d": ([ctypes.POINTER(_vp), _u32, _u64p, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp], _int),
+    "bj_non_residues_h": ([_u32, _u32, _u64p], _int),
     "bj_fill_synthetic_d": ([_vp, _u32, _sz, _u32, _u64, _u64, _vp], _int),
     "bj_gl_op_d": ([_int, _vp, _vp, _vp, _sz, _vp], _int),
 }

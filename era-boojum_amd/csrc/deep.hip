@@ -17,6 +17,7 @@
 #include <stdio.h>
 #include "gl.hpp"
 #include "gl_asm.hpp"
+#include "ext2.hpp"
 #include "bj_internal.hpp"
 #include "../../include/boojum_mi355x.h"
 
@@ -24,29 +25,8 @@ namespace bj {
 
 namespace {
 
-constexpr uint64_t EXT2_NON_RESIDUE = 7;  // GoldilocksExt2::NON_RESIDUE (extension.rs:14-16)
-static_assert(EXT2_NON_RESIDUE == (1u << 3) - 1, "times7 multiplies by the non-residue as 2^3 v - v");
-
-__host__ __device__ __forceinline__ uint64_t times7(uint64_t v) { return gl::sub(gl::mul_pow2_small(v, 3), v); }
-__host__ __device__ __forceinline__ uint64_t neg(uint64_t v) { return gl::sub(0, v); }
-
-// a^(p - 2), p - 2 = (2^31 - 1) 2^33 + (2^32 - 1): 64 squarings and 10 products
-__device__ __forceinline__ uint64_t sqn(uint64_t a, int k) {
-    for (int i = 0; i < k; i++) a = gl::mul(a, a);
-    return a;
-}
-__device__ uint64_t inv_chain(uint64_t a) {
-    const uint64_t t2 = gl::mul(sqn(a, 1), a);       // a^(2^2 - 1)
-    const uint64_t t4 = gl::mul(sqn(t2, 2), t2);     // a^(2^4 - 1)
-    const uint64_t t8 = gl::mul(sqn(t4, 4), t4);
-    const uint64_t t16 = gl::mul(sqn(t8, 8), t8);
-    const uint64_t t24 = gl::mul(sqn(t16, 8), t8);
-    const uint64_t t28 = gl::mul(sqn(t24, 4), t4);
-    const uint64_t t30 = gl::mul(sqn(t28, 2), t2);
-    const uint64_t t31 = gl::mul(sqn(t30, 1), a);    // a^(2^31 - 1)
-    const uint64_t t32 = gl::mul(sqn(t31, 1), a);    // a^(2^32 - 1)
-    return gl::mul(sqn(t31, 33), t32);
-}
+// the non-residue 7, times7, neg and the inversion chain inv_chain
+using namespace ext2;
 
 // Powers of one root w by 8-bit digits of the exponent: tab[256 k + b] = w^(b 2^(8k)), k < 4, and
 // the digit-0 entries carry `scale` as well, so scale * w^e is three products for any e < 2^32.

@@ -520,6 +520,59 @@ int bj_deep_quotient_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride,
                        size_t row0, size_t n_rows, uint64_t* dst0, uint64_t* dst1, int accumulate,
                        void* stream);
 
+/* ------------------------------------------------------------------ stage 2 */
+/* The columns of the stage-2 oracle (prover.rs:360-438, committed at :505-554), computed from
+ * witness and setup columns that stay on the device: the copy-permutation grand product with its
+ * partial products, and the lookup argument's encoding polynomials.  Added after 2.6; detect by
+ * symbol (bj_abi_version() is unchanged).  Everything is over the main domain in natural order
+ * (row i is x_i = w_n^i: no coset, no LDE, no bit reversal).  Inputs may be any u64 representative;
+ * outputs are canonical.  Asynchronous on `stream`, no allocation and no synchronisation, so the
+ * calls can be captured in a HIP graph.
+ * status_d: device u64[4], rewritten by every call: [0], [1] the product of a over all rows
+ * (bj_copy_permutation_d; 0 for the lookup call), [2] the number of zero denominators, [3] 0. */
+
+/* compute_partial_products_in_extension (cs/implementations/copy_permutation.rs:649-774, over
+ * pointwise_rational_in_extension :114-248, pointwise_product_in_extension :298-365 and
+ * shifted_grand_product_in_extension :425-510; x_poly of utils.rs:690-721), as called at
+ * prover.rs:360-392.  With m = ceil(n_cols / chunk) chunks of `chunk` columns (the last may be shorter):
+ *   r_j[i] = prod_{c in chunk j} (w_c[i] + beta k_c x_i + gamma) / (w_c[i] + beta sigma_c[i] + gamma)
+ *   a[i]   = prod_j r_j[i],   z[0] = 1,   z[i] = prod_{t < i} a[t],
+ *   p_j[i] = z[i] prod_{t <= j} r_t[i],   j = 0 .. m - 2
+ * in GoldilocksExt2 (u^2 = 7).  vars, sigmas: n_cols device columns of 2^log_n rows, column c at
+ * + c * stride.  non_residues: HOST array k_c (bj_non_residues_h).  chunk: the quotient degree, a
+ * power of two.  out: 2 m device columns of stride out_stride: z.c0, z.c1, p_0.c0, p_0.c1, ...;
+ * they are the call's working memory too.  With m = 1 there is no intermediate: the reference
+ * returns its lone per-chunk product there (:747-749), which
+ * num_intermediate_partial_product_relations (:14-28) and so the verifier do not count.
+ * Where the reference panics, this call reports: status_d[0..1] is the product over all rows
+ * (the reference asserts it is one, :485), and a chunk denominator that is zero (batch inverse
+ * panic, utils.rs:425-427) is counted in status_d[2] and its r_j[i] taken as 0.
+ * BJ_EINVAL: log_n > 32, n_cols = 0, chunk no power of two, a stride below 2^log_n, a null pointer. */
+int bj_copy_permutation_d(const uint64_t* vars, size_t vars_stride, const uint64_t* sigmas, size_t sigmas_stride,
+                          uint32_t n_cols, uint32_t log_n, const uint64_t* non_residues, uint64_t beta0,
+                          uint64_t beta1, uint64_t gamma0, uint64_t gamma1, uint32_t chunk, uint64_t* out,
+                          size_t out_stride, uint64_t* status_d, void* stream);
+
+/* The one operation behind compute_lookup_poly_pairs_specialized
+ * (cs/implementations/lookup_argument_in_ext.rs:320-700):
+ *   out[i] = f[i] / (beta + sum_{t < n_src} g_t srcs[t][i]),  i < 2^log_n,  in GoldilocksExt2.
+ * srcs: HOST array of n_src <= 16 device column pointers (they may belong to different buffers:
+ * variable columns and a setup constant column, :536-554); g: HOST array of the n_src Ext2
+ * coefficients (g_t.c0, g_t.c1), the powers of gamma of :402-418; f: a device column or NULL for 1.
+ * A witness encoding (:521-632) is f = NULL over the sub-argument's columns, a multiplicity
+ * encoding (:423-518, :635-672) f = the multiplicity column over the table columns.  A zero
+ * denominator gives 0 and is counted in status_d[2].
+ * BJ_EINVAL: log_n > 32, n_src outside 1..16, a null pointer other than f. */
+int bj_lookup_encoding_d(const uint64_t* const* srcs, uint32_t n_src, const uint64_t* g, uint64_t beta0,
+                         uint64_t beta1, const uint64_t* f, uint32_t log_n, uint64_t* out_c0, uint64_t* out_c1,
+                         uint64_t* status_d, void* stream);
+
+/* non_residues_for_copy_permutation(2^log_n, num) (copy_permutation.rs:512-522): out[0] = 1, then
+ * make_non_residues(num - 1, 2^log_n) (utils.rs:636-688): the smallest quadratic non-residues
+ * 2, 3, ... outside the domain and in pairwise distinct cosets of it.  Host only, no device call.
+ * BJ_EINVAL: log_n > 32, num = 0, null out. */
+int bj_non_residues_h(uint32_t num, uint32_t log_n, uint64_t* out);
+
 /* ------------------------------------------------------------- utility */
 
 /* Batched field arithmetic through the device field layer (utility for parity tests of
