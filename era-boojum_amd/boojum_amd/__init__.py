@@ -16,8 +16,10 @@ package is the host-side mirror of the reference's interface for that path:
   stage2   compute_partial_products_in_extension, compute_lookup_poly_pairs_specialized,
            second_stage_trace                                (copy_permutation.rs:649-774,
                                                               lookup_argument_in_ext.rs:320-700, prover.rs:360-438)
+  queries  QueryOracle, construct_queries, OracleQuery, single_round_queries, fri_plan
+                                                             (prover.rs:2161-2266, proof.rs:48-116)
 """
 from ._lib import BoojumError, load  # noqa: F401
 from .field import P, GENERATOR  # noqa: F401
 
-__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "field", "BoojumError", "load", "P", "GENERATOR"]
+__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "queries", "field", "BoojumError", "load", "P", "GENERATOR"]

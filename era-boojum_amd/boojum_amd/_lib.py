@@ -20,6 +20,18 @@ _u64p = ctypes.POINTER(ctypes.c_uint64)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                ctypes.c_size_t, ctypes.c_void_p)
 
+
+
+class QueryOracleDesc(ctypes.Structure):
+    """bj_query_oracle_t (include/boojum_mi355x.h), 56 bytes."""
+    _fields_ = [("src", _vp), ("col_stride", _sz), ("n_cols", _u32), ("log_elems_per_leaf", _u32),
+                ("leaves", _vp), ("nodes", _vp), ("n_leaves", _u64), ("cap_size", _u32), ("index_shift", _u32)]
+
+
+assert ctypes.sizeof(QueryOracleDesc) == 56
+QUERY_MAX_ORACLES = 16  # BJ_QUERY_MAX_ORACLES
+_qop = ctypes.POINTER(QueryOracleDesc)
+
 # name -> argtypes (restype int unless noted).  Every symbol the header declares.
 SIGNATURES = {
     "bj_last_error": ([], ctypes.c_char_p),
@@ -92,6 +104,8 @@ SIGNATURES = {
                                _vp], _int),
     "bj_lookup_encoding_d": ([ctypes.POINTER(_vp), _u32, _u64p, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp], _int),
     "bj_non_residues_h": ([_u32, _u32, _u64p], _int),
+    "bj_oracle_query_words": ([_qop], _sz),
+    "bj_oracle_queries_d": ([_qop, _u32, _vp, _u32, _vp, _sz, _vp, _vp], _int),
     "bj_fill_synthetic_d": ([_vp, _u32, _sz, _u32, _u64, _u64, _vp], _int),
     "bj_gl_op_d": ([_int, _vp, _vp, _vp, _sz, _vp], _int),
 }

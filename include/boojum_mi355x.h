@@ -573,6 +573,60 @@ int bj_lookup_encoding_d(const uint64_t* const* srcs, uint32_t n_src, const uint
  * BJ_EINVAL: log_n > 32, num = 0, null out. */
 int bj_non_residues_h(uint32_t num, uint32_t log_n, uint64_t* out);
 
+/* ------------------------------------------------------------------ queries */
+/* The query phase (prover.rs:2161-2266): every OracleQuery of a proof -- the leaf's elements
+ * (QuerySource::get_elements, fri/mod.rs:683-927) and its Merkle path (get_proof,
+ * merkle_tree.rs:462-480; OracleQuery::construct, proof.rs:64-97) -- for all oracles and all query
+ * indices in one launch, from LDEs and trees that stay on the device.  Added after 2.6; detect by
+ * symbol (bj_abi_version() is unchanged).  Everything is copied bit for bit, with no arithmetic:
+ * elements come back as they are stored and the [u8; 32] digests of Blake2s256 / Keccak256 trees
+ * are not reduced.
+ *
+ * A query index is the flat leaf index coset * n + row of the committed LDE domain, the index of
+ * bj_merkle_leaves_d.  An oracle's tree index is index >> index_shift; that one shift is the
+ * reference's whole index arithmetic.  For FRI oracle k of the schedule s_0, s_1, ...
+ * (prover.rs:2226-2254, proof.rs:89-91):
+ *   domain_size_k = n >> (s_0 + ... + s_{k-1}),  inner_k = inner >> (s_0 + ... + s_{k-1}),
+ *   tree_idx = (coset << (log2 domain_size_k - s_k)) + (inner_k >> s_k)
+ * and since inner < n this is (coset * n + inner) >> (s_0 + ... + s_k). */
+#define BJ_QUERY_MAX_ORACLES 16
+typedef struct bj_query_oracle {
+    const uint64_t* src;         /* column 0 of the leaf sources (device); NULL iff n_cols == 0 */
+    size_t col_stride;           /* elements between columns */
+    uint32_t n_cols;             /* 0: path only */
+    uint32_t log_elems_per_leaf; /* e: leaf L hashes, per column in order, src[c*col_stride + (L<<e) + t], t < 2^e
+                                    (bj_merkle_leaves_d: e = 0; bj_merkle_leaves_chunked_d: 2^e = elems_per_leaf) */
+    const uint64_t* leaves;      /* n_leaves x 4 */
+    const uint64_t* nodes;       /* (n_leaves - cap_size) x 4, bj_merkle_nodes_d's layout; may be NULL iff
+                                    n_leaves == cap_size */
+    uint64_t n_leaves;
+    uint32_t cap_size;
+    uint32_t index_shift;        /* tree index = query index >> index_shift */
+} bj_query_oracle_t;
+
+/* Words of one query's record of oracle o: (n_cols << e) + 4 + 4 * depth, depth =
+ * log2(n_leaves / cap_size).  0 for a null o or sizes that are no powers of two.  Host only. */
+size_t bj_oracle_query_words(const bj_query_oracle_t* o);
+
+/* oracles: HOST array of n_oracles descriptors (they travel to the kernel by value); indices_d:
+ * n_queries device u64.  Oracle o's block starts at out_d + n_queries * sum_{o' < o} W_o', W =
+ * bj_oracle_query_words, and query q's record at + q * W_o.  A record is the leaf's elements
+ * (column-major: column 0's 2^e elements, then column 1's, ..., the order of get_elements), the
+ * leaf hash (4 words), then the depth siblings in get_proof order: sibling l is entry (t >> l) ^ 1
+ * of level l, t the tree index, level 0 the leaves and level l >= 1 after the lower levels in
+ * nodes.  n_leaves == cap_size (the last FRI oracle, fri/mod.rs:258-266) gives an empty path.
+ * Every oracle of a call covers the same domain: n_leaves << index_shift is equal for all.
+ * status_d: device u64[4], rewritten by every call: [0] the number of query indices >=
+ * n_leaves << index_shift, [1] the position of the first such index or ~0, [2] = [3] = 0.  Such a
+ * query reads nothing and all its records are zero.
+ * One launch whatever n_oracles and n_queries; asynchronous on `stream`, no allocation and no
+ * synchronisation, so the call can be captured in a HIP graph.
+ * BJ_EINVAL: n_oracles outside 1..16, n_queries = 0, a null pointer other than the two allowed
+ * above, n_leaves or cap_size no power of two, n_leaves < cap_size, col_stride < n_leaves << e
+ * with n_cols > 0, domains that disagree, out_words below n_queries * sum_o W_o. */
+int bj_oracle_queries_d(const bj_query_oracle_t* oracles, uint32_t n_oracles, const uint64_t* indices_d,
+                        uint32_t n_queries, uint64_t* out_d, size_t out_words, uint64_t* status_d, void* stream);
+
 /* ------------------------------------------------------------- utility */
 
 /* Batched field arithmetic through the device field layer (utility for parity tests of
