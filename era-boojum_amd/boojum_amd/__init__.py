@@ -18,8 +18,9 @@ package is the host-side mirror of the reference's interface for that path:
                                                               lookup_argument_in_ext.rs:320-700, prover.rs:360-438)
   queries  QueryOracle, construct_queries, OracleQuery, single_round_queries, fri_plan
                                                              (prover.rs:2161-2266, proof.rs:48-116)
+  pow      PoWRunner, Blake2s256, Keccak256, NoPow, search  (cs/implementations/pow.rs, prover.rs:2107-2133)
 """
 from ._lib import BoojumError, load  # noqa: F401
 from .field import P, GENERATOR  # noqa: F401
 
-__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "queries", "field", "BoojumError", "load", "P", "GENERATOR"]
+__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "queries", "pow", "field", "BoojumError", "load", "P", "GENERATOR"]

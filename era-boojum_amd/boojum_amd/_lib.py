@@ -106,6 +106,9 @@ SIGNATURES = {
     "bj_non_residues_h": ([_u32, _u32, _u64p], _int),
     "bj_oracle_query_words": ([_qop], _sz),
     "bj_oracle_queries_d": ([_qop, _u32, _vp, _u32, _vp, _sz, _vp, _vp], _int),
+    "bj_pow_search_d": ([_u32, ctypes.c_char_p, _sz, _u32, _u64, _u64, _vp, _vp], _int),
+    "bj_pow_run_h": ([_u32, ctypes.c_char_p, _sz, _u32, _u64p], _int),
+    "bj_pow_verify_h": ([_u32, ctypes.c_char_p, _sz, _u32, _u64], _int),
     "bj_fill_synthetic_d": ([_vp, _u32, _sz, _u32, _u64, _u64, _vp], _int),
     "bj_gl_op_d": ([_int, _vp, _vp, _vp, _sz, _vp], _int),
 }

@@ -627,6 +627,39 @@ size_t bj_oracle_query_words(const bj_query_oracle_t* o);
 int bj_oracle_queries_d(const bj_query_oracle_t* oracles, uint32_t n_oracles, const uint64_t* indices_d,
                         uint32_t n_queries, uint64_t* out_d, size_t out_words, uint64_t* status_d, void* stream);
 
+/* ------------------------------------------------------------------ proof of work */
+/* PoWRunner (cs/implementations/pow.rs:7-32) for Blake2s256 (pow.rs:51-135) and Keccak256
+ * (pow.rs:137-221), the step between the last FRI oracle and the queries (prover.rs:2107-2133).
+ * Added after 2.6; detect by symbol (bj_abi_version() is unchanged).
+ *
+ * A nonce passes when u64::from_le_bytes(H(seed || nonce.to_le_bytes())[..8]).trailing_zeros() >=
+ * pow_bits (pow.rs:63-67, 127-133), pow_bits <= 32 (pow.rs:53).  H is Blake2s256 (RFC 7693, unkeyed)
+ * or Keccak256 (rate 136, domain byte 0x01).  The seed the prover passes is 5 field elements
+ * (prover.rs:2115-2118), each as_u64_reduced().to_le_bytes() (pow.rs:10-12): 40 bytes; any length
+ * is accepted.  These entries always return the SMALLEST passing nonce of the range they search:
+ * that is the reference's serial scan for pow_bits <= 16 (pow.rs:58-71) and one of the answers
+ * its race of 2^16-nonce slices may give above that (pow.rs:76-119).  The nonce 2^64 - 1 is never
+ * tested: it is the reference's "no result" (pow.rs:48, 61). */
+#define BJ_POW_NO_RESULT UINT64_MAX
+/* hasher: BJ_HASHER_BLAKE2S or BJ_HASHER_KECCAK256; BJ_HASHER_POSEIDON2 -> BJ_EINVAL (the reference has no such runner) */
+
+/* One launch over [first_nonce, first_nonce + n_nonces): *result_d = min(*result_d, smallest passing nonce of the window).
+ * The caller initialises *result_d (BJ_POW_NO_RESULT for a fresh search).  seed is host memory, read before the call
+ * returns.  Stream-ordered, no allocation, no synchronise.
+ * BJ_EINVAL: pow_bits > 32, a hasher other than the two above, n_nonces == 0, first_nonce + n_nonces > 2^64 - 1, a null
+ * seed with seed_len > 0, a null result_d. */
+int bj_pow_search_d(uint32_t hasher, const uint8_t* seed, size_t seed_len, uint32_t pow_bits,
+                    uint64_t first_nonce, uint64_t n_nonces, uint64_t* result_d, void* stream);
+
+/* PoWRunner::run_from_bytes (pow.rs:52-124, 141-213): the smallest passing nonce >= 0, found window by window;
+ * synchronous on the calling thread's library stream.  pow_bits == 0: nonce 0, no launch (the prover skips PoW then,
+ * prover.rs:2109).  *nonce_out = BJ_POW_NO_RESULT when no nonce below 2^64 - 1 passes. */
+int bj_pow_run_h(uint32_t hasher, const uint8_t* seed, size_t seed_len, uint32_t pow_bits, uint64_t* nonce_out);
+
+/* PoWRunner::verify_from_bytes (pow.rs:126-134, 215-221): 1 passes, 0 fails, negative on an argument error.  Host
+ * code only: no device call. */
+int bj_pow_verify_h(uint32_t hasher, const uint8_t* seed, size_t seed_len, uint32_t pow_bits, uint64_t nonce);
+
 /* ------------------------------------------------------------- utility */
 
 /* Batched field arithmetic through the device field layer (utility for parity tests of
