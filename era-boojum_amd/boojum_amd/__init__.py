@@ -16,6 +16,10 @@ package is the host-side mirror of the reference's interface for that path:
   stage2   compute_partial_products_in_extension, compute_lookup_poly_pairs_specialized,
            second_stage_trace                                (copy_permutation.rs:649-774,
                                                               lookup_argument_in_ext.rs:320-700, prover.rs:360-438)
+  quotient compute_quotient_terms_in_extension, compute_quotient_terms_for_lookup_specialized,
+           divide_by_vanishing_for_bitreversed_coset_enumeration, quotient_monomials,
+           quotient_from_arguments                           (copy_permutation.rs:1000-1249,
+                                                              lookup_argument_in_ext.rs:949-1310, prover.rs:1111-1467)
   queries  QueryOracle, construct_queries, OracleQuery, single_round_queries, fri_plan
                                                              (prover.rs:2161-2266, proof.rs:48-116)
   pow      PoWRunner, Blake2s256, Keccak256, NoPow, search  (cs/implementations/pow.rs, prover.rs:2107-2133)
@@ -23,4 +27,4 @@ package is the host-side mirror of the reference's interface for that path:
 from ._lib import BoojumError, load  # noqa: F401
 from .field import P, GENERATOR  # noqa: F401
 
-__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "queries", "pow", "field", "BoojumError", "load", "P", "GENERATOR"]
+__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "quotient", "queries", "pow", "field", "BoojumError", "load", "P", "GENERATOR"]

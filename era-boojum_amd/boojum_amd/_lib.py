@@ -104,6 +104,12 @@ SIGNATURES = {
                                _vp], _int),
     "bj_lookup_encoding_d": ([ctypes.POINTER(_vp), _u32, _u64p, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp], _int),
     "bj_non_residues_h": ([_u32, _u32, _u64p], _int),
+    "bj_quotient_copy_permutation_d": ([_vp, _sz, _vp, _sz, _vp, _sz, _u32, _u32, _u32, _u64p, _u64, _u64, _u64, _u64,
+                                        _u64p, _vp, _vp, _vp], _int),
+    "bj_quotient_lookup_term_d": ([ctypes.POINTER(_vp), _u32, _u64p, _u64, _u64, _vp, _vp, _vp, _u64, _u64, _u32, _u32,
+                                   _vp, _vp, _vp], _int),
+    "bj_quotient_divide_vanishing_d": ([_vp, _vp, _u32, _u32, _vp], _int),
+    "bj_vanishing_inverses_h": ([_u32, _u32, _u64p], _int),
     "bj_oracle_query_words": ([_qop], _sz),
     "bj_oracle_queries_d": ([_qop, _u32, _vp, _u32, _vp, _sz, _vp, _vp], _int),
     "bj_pow_search_d": ([_u32, ctypes.c_char_p, _sz, _u32, _u64, _u64, _vp, _vp], _int),

@@ -1,8 +1,11 @@
 // GoldilocksExt2 = F[u] / (u^2 - 7) (field/goldilocks/extension.rs:14-40) on top of gl.hpp: what
-// deep.hip and stage2.hip share.  Values are (c0, c1) pairs of u64 representatives, not
+// deep.hip, stage2.hip and quotient.hip share.  Values are (c0, c1) pairs of u64 representatives, not
 // necessarily canonical; a kernel canonicalises what it writes.
 #pragma once
 #include "gl.hpp"
+#if defined(__HIPCC__)
+#include "gl_asm.hpp"
+#endif
 
 namespace bj {
 namespace ext2 {
@@ -25,6 +28,21 @@ GL_FN uint64_t norm(E2 a) { return gl::sub(gl::mul(a.c0, a.c0), times7(gl::mul(a
 GL_FN bool is_zero(E2 a) { return (gl::canon(a.c0) | gl::canon(a.c1)) == 0; }
 
 #if defined(__HIPCC__)
+__device__ __forceinline__ uint32_t lo32(uint64_t v) { return (uint32_t)v; }
+__device__ __forceinline__ uint32_t hi32(uint64_t v) { return (uint32_t)(v >> 32); }
+__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
+
+// a * b with the four products as one batch of the 14-instruction form (gl_asm.hpp): the product
+// of a walk over columns (stage2.hip, quotient.hip)
+__device__ __forceinline__ E2 mul_x4(E2 a, E2 b) {
+    uint32_t zl[4], zh[4];
+    glasm::mul_x4(lo32(a.c0), hi32(a.c0), lo32(b.c0), hi32(b.c0), zl[0], zh[0], lo32(a.c1), hi32(a.c1), lo32(b.c1),
+                  hi32(b.c1), zl[1], zh[1], lo32(a.c0), hi32(a.c0), lo32(b.c1), hi32(b.c1), zl[2], zh[2], lo32(a.c1),
+                  hi32(a.c1), lo32(b.c0), hi32(b.c0), zl[3], zh[3]);
+    return {gl::add(u64_of(zl[0], zh[0]), times7(u64_of(zl[1], zh[1]))),
+            gl::add(u64_of(zl[2], zh[2]), u64_of(zl[3], zh[3]))};
+}
+
 // a^(p - 2), p - 2 = (2^31 - 1) 2^33 + (2^32 - 1): 64 squarings and 10 products
 __device__ __forceinline__ uint64_t sqn(uint64_t a, int k) {
     for (int i = 0; i < k; i++) a = gl::mul(a, a);

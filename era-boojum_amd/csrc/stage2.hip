@@ -59,20 +59,7 @@ struct CpConsts {
     uint64_t wpow[32];    // w_n^(2^b)
 };
 
-__device__ __forceinline__ uint32_t lo32(uint64_t v) { return (uint32_t)v; }
-__device__ __forceinline__ uint32_t hi32(uint64_t v) { return (uint32_t)(v >> 32); }
-__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
-
-// a * b with the four products as one batch of the 14-instruction form (gl_asm.hpp): the column
-// walk's product
-__device__ __forceinline__ E2 mul_x4(E2 a, E2 b) {
-    uint32_t zl[4], zh[4];
-    glasm::mul_x4(lo32(a.c0), hi32(a.c0), lo32(b.c0), hi32(b.c0), zl[0], zh[0], lo32(a.c1), hi32(a.c1), lo32(b.c1),
-                  hi32(b.c1), zl[1], zh[1], lo32(a.c0), hi32(a.c0), lo32(b.c1), hi32(b.c1), zl[2], zh[2], lo32(a.c1),
-                  hi32(a.c1), lo32(b.c0), hi32(b.c0), zl[3], zh[3]);
-    return {gl::add(u64_of(zl[0], zh[0]), times7(u64_of(zl[1], zh[1]))),
-            gl::add(u64_of(zl[2], zh[2]), u64_of(zl[3], zh[3]))};
-}
+// lo32, hi32, u64_of and the column walk's product mul_x4 are ext2.hpp's
 
 __device__ __forceinline__ E2 shfl_up(E2 v, int d) {
     return {(uint64_t)__shfl_up((unsigned long long)v.c0, d, 64), (uint64_t)__shfl_up((unsigned long long)v.c1, d, 64)};

@@ -573,6 +573,92 @@ int bj_lookup_encoding_d(const uint64_t* const* srcs, uint32_t n_src, const uint
  * BJ_EINVAL: log_n > 32, num = 0, null out. */
 int bj_non_residues_h(uint32_t num, uint32_t log_n, uint64_t* out);
 
+/* ------------------------------------------------------------------ quotient */
+/* The step between the stage-2 commit and the quotient commit (prover.rs:1111-1467): the
+ * copy-permutation and lookup terms over the LDE domain, the division by the vanishing polynomial,
+ * and the way to monomials.  The gate terms depend on the circuit and are the caller's: they enter
+ * as the initial contents of the accumulator, as the reference hands its quotient_c0s /
+ * quotient_c1s to this block (prover.rs:1161-1175); a caller without any zeroes it.  Added after
+ * 2.6; detect by symbol (bj_abi_version() is unchanged).  Inputs may be any u64 representative;
+ * outputs are canonical.  Asynchronous on `stream`, no allocation and no synchronisation, so the
+ * calls can be captured in a HIP graph.
+ *
+ * Domain and layout.  q = 2^log_q is the quotient degree, at most BJ_QUOTIENT_MAX_DEGREE (the
+ * per-coset constants travel in the kernel arguments).  The accumulator dst0 / dst1 (the Ext2
+ * halves) holds q * n words each in leaf order L = coset * n + row, x_L = 7 * w_{nq}^{bitrev_{log
+ * nq}(L)}, bj_deep_quotient_d's x_L.  A source column is a column of bj_lde_d's output at D >= q,
+ * given by the address of its coset 0: its value at point L is column[L], because the first q
+ * cosets of a bit-reversed D-LDE are the q-LDE (subset_for_degree, lde.rs:298-308).  Columns of
+ * one tensor are `stride` = n * D words apart.
+ *
+ * From stage 2 to bj_monomials_to_lde_d (the quotient commit, prover.rs:1471-1495):
+ *   bj_copy_permutation_d, bj_lookup_encoding_d    -> the stage-2 columns      (n each)
+ *   bj_lde_d at D >= q on them, the variables, the sigmas, ...                 (D * n each)
+ *   dst0, dst1 = 0 or the gate terms                                           (q * n each)
+ *   bj_quotient_copy_permutation_d, bj_quotient_lookup_term_d per lookup term  dst += terms
+ *   bj_quotient_divide_vanishing_d                                             dst /= x^n - 1
+ *   bj_bitreverse_enumeration_d(dst, 2 columns, log_n + log_q): the leaf order is the bit-reversed
+ *     enumeration of the whole domain of q * n points (flatten_presumably_bitreversed,
+ *     prover.rs:1409-1410), then bj_ifft_natural_to_natural_d(.., log_n + log_q, coset 7)
+ *     (prover.rs:1421-1422): q * n monomial coefficients per half.  Their last q are zero for a
+ *     satisfied circuit (the reference asserts the last one, "unsatisfied", prover.rs:1424-1439).
+ *   chunk i is the slice [i * n, (i + 1) * n) of each half, and the quotient oracle's columns are
+ *     chunk_0.c0, chunk_0.c1, chunk_1.c0, ... (prover.rs:1454-1467). */
+#define BJ_QUOTIENT_MAX_DEGREE 128u
+
+/* The (z(x) - 1) L_1(x) term (prover.rs:1148-1227; unnormalized_l1_inverse, utils.rs:1585-1665)
+ * and compute_quotient_terms_in_extension (cs/implementations/copy_permutation.rs:1000-1249), all
+ * m = ceil(n_cols / q) relations, one read and one write of the accumulator.  Per point L:
+ *   t_0     = alpha_0 (z(x) - 1) (x^n - 1) / (x - 1)
+ *   t_{j+1} = alpha_{j+1} (lhs_j prod_{c in chunk j} (w_c + beta sigma_c + gamma)
+ *                          - rhs_j prod_{c in chunk j} (w_c + beta k_c x + gamma)),   j < m
+ *   dst    += sum t
+ * in GoldilocksExt2, with rhs = [z, p_0, .., p_{m-2}], lhs = [p_0, .., p_{m-2}, z(w x)] and chunk j
+ * the columns [j q, min(n_cols, (j + 1) q)), bj_copy_permutation_d's chunks at chunk = q.
+ * vars, sigmas: n_cols LDE columns each.  stage2: the LDE of bj_copy_permutation_d's 2 m output
+ * columns in its order (z.c0, z.c1, p_0.c0, ...).  z(w x) is read in place, at row
+ * bitrev(bitrev(row) + 1 mod n) of the same coset (the reference clones the column,
+ * shift_by_omega_assuming_bitreversed, utils.rs:1245-1271).  That row lies half a coset away, so
+ * a row window is not self-contained: the call covers the whole domain and takes no window.
+ * non_residues: HOST array k_c (bj_non_residues_h).  alphas: HOST array of the m + 1 Ext2
+ * challenges (c0, c1), the L_1 term's first.  A trace wider than one launch's kernel arguments
+ * hold (128 columns or 64 relations) takes several launches on `stream` that meet on chunk
+ * boundaries; only the first adds t_0.
+ * BJ_EINVAL: log_n + log_q > 32, q > BJ_QUOTIENT_MAX_DEGREE, n_cols = 0, a stride below q * n, a
+ * null pointer. */
+int bj_quotient_copy_permutation_d(const uint64_t* vars, size_t vars_stride, const uint64_t* sigmas,
+                                   size_t sigmas_stride, const uint64_t* stage2, size_t stage2_stride, uint32_t n_cols,
+                                   uint32_t log_n, uint32_t log_q, const uint64_t* non_residues, uint64_t beta0,
+                                   uint64_t beta1, uint64_t gamma0, uint64_t gamma1, const uint64_t* alphas,
+                                   uint64_t* dst0, uint64_t* dst1, void* stream);
+
+/* The one operation behind both loops of compute_quotient_terms_for_lookup_specialized
+ * (cs/implementations/lookup_argument_in_ext.rs:949-1310):
+ *   dst[L] += alpha (E[L] (beta + sum_{t < n_src} g_t srcs[t][L]) - f[L]),  L < q * n.
+ * srcs: HOST array of n_src <= 16 device pointers to LDE columns (they may belong to different
+ * buffers); g: HOST array of the n_src Ext2 coefficients, the powers of gamma (:1000-1014);
+ * e_c0, e_c1: the LDE columns of the encoding polynomial; f: an LDE column or NULL for 1.
+ * A witness-encoding term (:1115-1229) is f = NULL over the sub-argument's variable columns (and
+ * the table-id constant column when it is shared, :1135-1138) with E = A_s; the multiplicity term
+ * (:1231-1310) is f = the multiplicity column over the table columns with E = B, so the
+ * reference's aggregated_lookup_columns buffer (:1023-1104) is never materialised.
+ * BJ_EINVAL: log_n + log_q > 32, q > BJ_QUOTIENT_MAX_DEGREE, n_src outside 1..16, a null pointer
+ * other than f. */
+int bj_quotient_lookup_term_d(const uint64_t* const* srcs, uint32_t n_src, const uint64_t* g, uint64_t beta0,
+                              uint64_t beta1, const uint64_t* e_c0, const uint64_t* e_c1, const uint64_t* f,
+                              uint64_t alpha0, uint64_t alpha1, uint32_t log_n, uint32_t log_q, uint64_t* dst0,
+                              uint64_t* dst1, void* stream);
+
+/* divide_by_vanishing_for_bitreversed_coset_enumeration (utils.rs:770-817), both halves in one
+ * launch: dst[L] *= inv[L >> log_n] with bj_vanishing_inverses_h's constants, which the call
+ * computes itself.  BJ_EINVAL: log_n + log_q > 32, q > BJ_QUOTIENT_MAX_DEGREE, a null pointer. */
+int bj_quotient_divide_vanishing_d(uint64_t* dst0, uint64_t* dst1, uint32_t log_n, uint32_t log_q, void* stream);
+
+/* out[i] = 1 / (7^n w_{nq}^{n bitrev_{log q}(i)} - 1), i < 2^log_q: the inverse of x^n - 1 on coset
+ * i (utils.rs:788-799), canonical.  Host only, no device call, any log_q with log_n + log_q <= 32.
+ * BJ_EINVAL: log_n + log_q > 32, null out. */
+int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out);
+
 /* ------------------------------------------------------------------ queries */
 /* The query phase (prover.rs:2161-2266): every OracleQuery of a proof -- the leaf's elements
  * (QuerySource::get_elements, fri/mod.rs:683-927) and its Merkle path (get_proof,
