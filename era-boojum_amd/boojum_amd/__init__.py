@@ -20,6 +20,9 @@ package is the host-side mirror of the reference's interface for that path:
            divide_by_vanishing_for_bitreversed_coset_enumeration, quotient_monomials,
            quotient_from_arguments                           (copy_permutation.rs:1000-1249,
                                                               lookup_argument_in_ext.rs:949-1310, prover.rs:1111-1467)
+  gates    Index, Relation, TracingField, capture, GatePlacement, GateSet, evaluate_gate_terms and a
+           small library of evaluators                       (gpu_synthesizer/mod.rs, prover.rs:560-1085,
+                                                              buffering_source.rs:157-377, cs/gates/*.rs)
   queries  QueryOracle, construct_queries, OracleQuery, single_round_queries, fri_plan
                                                              (prover.rs:2161-2266, proof.rs:48-116)
   pow      PoWRunner, Blake2s256, Keccak256, NoPow, search  (cs/implementations/pow.rs, prover.rs:2107-2133)
@@ -27,4 +30,4 @@ package is the host-side mirror of the reference's interface for that path:
 from ._lib import BoojumError, load  # noqa: F401
 from .field import P, GENERATOR  # noqa: F401
 
-__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "quotient", "queries", "pow", "field", "BoojumError", "load", "P", "GENERATOR"]
+__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "quotient", "gates", "queries", "pow", "field", "BoojumError", "load", "P", "GENERATOR"]

@@ -110,6 +110,11 @@ SIGNATURES = {
                                    _vp, _vp, _vp], _int),
     "bj_quotient_divide_vanishing_d": ([_vp, _vp, _u32, _u32, _vp], _int),
     "bj_vanishing_inverses_h": ([_u32, _u32, _u64p], _int),
+    "bj_gate_set_check_h": ([_u64p, _sz, _u64p], _int),
+    "bj_gate_set_upload_d": ([_u64p, _sz, ctypes.POINTER(_vp)], _int),
+    "bj_gate_set_release": ([_vp], _int),
+    "bj_quotient_gate_terms_d": ([_vp, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _u32, _u32, _u32,
+                                  _vp, _vp, _vp], _int),
     "bj_oracle_query_words": ([_qop], _sz),
     "bj_oracle_queries_d": ([_qop, _u32, _vp, _u32, _vp, _sz, _vp, _vp], _int),
     "bj_pow_search_d": ([_u32, ctypes.c_char_p, _sz, _u32, _u64, _u64, _vp, _vp], _int),

@@ -1,0 +1,720 @@
+"""The quotient's gate terms on the GPU: captured relation programs evaluated over LDE columns
+that stay on the device (bj_quotient_gate_terms_d, csrc/gates.hip).
+
+The circuit stays the caller's.  What the library takes is what the reference's
+gpu_synthesizer/mod.rs captures from an evaluator's `evaluate_once`:
+
+* `Index` and `Relation`, with the reference's names and fields (mod.rs:113-133);
+* `TracingField`, the counterpart of GpuSynthesizerFieldLike (mod.rs:199-338): a field-like whose
+  operations record relations instead of computing;
+* `capture(evaluator)` -> `GateProgram` (GPUDataCapture::from_evaluator, mod.rs:386-444): the
+  relations, the writes in push order and num_quotient_terms;
+* `GatePlacement`: a program with its repetitions, PerChunkOffset, initial offsets, selector path
+  and constants offset; `layout_general_purpose` / `specialized_placement` fill these in as the
+  reference does for a CSGeometry;
+* `compile_gate_set` (host only): slot allocation by liveness, the split into launches and the
+  upload image; `GateSet`: validation (bj_gate_set_check_h) and the one upload;
+* `evaluate_gate_terms`: dst += the gate terms, one launch per segment.
+
+The evaluators at the end are written as plain functions over a field-like, so the same function
+runs over `TracingField` to give the program and over any other field-like (the tests' Python
+integers) to give the values; each restates the reference's `evaluate_once`.  There is no CPU
+fallback: nothing here evaluates a program.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from ._lib import call, load
+from .field import P, stream_of, to_device
+
+MAX_SLOTS = 16              # BJ_GATE_MAX_SLOTS
+MAX_SELECTOR_DEPTH = 8      # BJ_GATE_MAX_SELECTOR_DEPTH
+MAX_INSTRUCTIONS = 4096     # BJ_GATE_MAX_INSTRUCTIONS, also the writes and the immediates of a launch
+MAX_GATES = 64              # BJ_GATE_MAX_GATES
+MAX_SEGMENTS = 64           # BJ_GATE_MAX_SEGMENTS
+MAGIC = 0x3153455441474A42  # "BJGATES1"
+
+_KINDS = ("VariablePoly", "WitnessPoly", "ConstantPoly", "TemporaryValue", "ConstantValue")
+_RELATIONS = ("Add", "Double", "Sub", "Negate", "Mul", "Square", "Inverse")
+_UNARY = ("Double", "Negate", "Square", "Inverse")
+
+
+class Index(tuple):
+    """gpu_synthesizer::Index: Index.VariablePoly(i), .WitnessPoly(i), .ConstantPoly(i),
+    .TemporaryValue(i), .ConstantValue(f)."""
+    __slots__ = ()
+    kind = property(lambda self: self[0])
+    value = property(lambda self: self[1])
+
+    def __repr__(self):
+        return "%s(%d)" % self
+
+
+class Relation(tuple):
+    """gpu_synthesizer::Relation: Relation.Add(a, b), .Double(a), .Sub(a, b), .Negate(a),
+    .Mul(a, b), .Square(a), .Inverse(a) over Index operands."""
+    __slots__ = ()
+    kind = property(lambda self: self[0])
+    operands = property(lambda self: tuple(self[1:]))
+
+    def __repr__(self):
+        return "%s(%s)" % (self[0], ", ".join(repr(o) for o in self[1:]))
+
+
+def _index_ctor(kind):
+    def make(value):
+        value = int(value)
+        if kind == "ConstantValue":
+            value %= P
+        elif value < 0:
+            raise ValueError("%s index must not be negative" % kind)
+        return Index((kind, value))
+    return staticmethod(make)
+
+
+def _relation_ctor(kind):
+    def make(*operands):
+        if len(operands) != (1 if kind in _UNARY else 2) or not all(isinstance(o, Index) for o in operands):
+            raise TypeError("Relation.%s takes %d Index operands" % (kind, 1 if kind in _UNARY else 2))
+        return Relation((kind,) + tuple(operands))
+    return staticmethod(make)
+
+
+for _k in _KINDS:
+    setattr(Index, _k, _index_ctor(_k))
+for _k in _RELATIONS:
+    setattr(Relation, _k, _relation_ctor(_k))
+
+
+class TracingContext:
+    """GPUVariablesGlobalContext (mod.rs:135-163): the temporary counter and the relations."""
+
+    def __init__(self):
+        self.counter = 0
+        self.relations = []   # (TemporaryValue index, Relation)
+
+    def push(self, relation):
+        idx = self.counter
+        self.counter += 1
+        self.relations.append((idx, relation))
+        return Index.TemporaryValue(idx)
+
+
+class TracingField:
+    """GpuSynthesizerFieldLike: the PrimeFieldLike surface the evaluators use.  The *_assign
+    operations, double, negate and square replace the receiver by a fresh temporary and return it,
+    as the reference's `&mut self` forms do; `copy()` is Rust's copy of a Copy value."""
+    __slots__ = ("idx", "ctx")
+
+    def __init__(self, idx, ctx):
+        self.idx, self.ctx = idx, ctx
+
+    def copy(self):
+        return TracingField(self.idx, self.ctx)
+
+    def zero(self):
+        return TracingField(Index.ConstantValue(0), self.ctx)
+
+    def one(self):
+        return TracingField(Index.ConstantValue(1), self.ctx)
+
+    def minus_one(self):
+        return TracingField(Index.ConstantValue(P - 1), self.ctx)
+
+    def constant(self, value):
+        return TracingField(Index.ConstantValue(value), self.ctx)
+
+    def _record(self, relation):
+        self.idx = self.ctx.push(relation)
+        return self
+
+    def add_assign(self, other):
+        return self._record(Relation.Add(self.idx, other.idx))
+
+    def sub_assign(self, other):
+        return self._record(Relation.Sub(self.idx, other.idx))
+
+    def mul_assign(self, other):
+        return self._record(Relation.Mul(self.idx, other.idx))
+
+    def double(self):
+        return self._record(Relation.Double(self.idx))
+
+    def negate(self):
+        return self._record(Relation.Negate(self.idx))
+
+    def square(self):
+        return self._record(Relation.Square(self.idx))
+
+    def inverse(self):
+        return TracingField(self.ctx.push(Relation.Inverse(self.idx)), self.ctx)
+
+    def mul_by_base(self, value):
+        """A product with a base-field constant (mul_all_by_base on a scalar field-like)."""
+        return self._record(Relation.Mul(self.idx, Index.ConstantValue(value)))
+
+    def mul_and_accumulate_into(self, a, b):
+        """PrimeFieldLike::mul_and_accumulate_into(acc = self, a, b) (field_like.rs:71-75)."""
+        tmp = a.copy()
+        tmp.mul_assign(b)
+        return self.add_assign(tmp)
+
+
+class TracingSource:
+    """GPUPolyStorage (mod.rs:19-91) at chunk offset zero: the repetition's offset is applied by
+    the device, not recorded."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def get_variable_value(self, i):
+        return TracingField(Index.VariablePoly(i), self.ctx)
+
+    def get_witness_value(self, i):
+        return TracingField(Index.WitnessPoly(i), self.ctx)
+
+    def get_constant_value(self, i):
+        return TracingField(Index.ConstantPoly(i), self.ctx)
+
+    def field(self):
+        """A field-like to draw zero / one / constants from."""
+        return TracingField(Index.ConstantValue(0), self.ctx)
+
+
+class TracingDestination:
+    """GPUPolyDestination (mod.rs:35-111)."""
+
+    def __init__(self):
+        self.writes = []
+
+    def push_evaluation_result(self, value):
+        self.writes.append(value.idx)
+
+
+class GateProgram:
+    """GPUDataCapture's relations, writes_per_repetition and num_quotient_terms."""
+
+    def __init__(self, relations, writes, num_quotient_terms, evaluator=None):
+        self.relations = list(relations)
+        self.writes = list(writes)
+        self.num_quotient_terms = num_quotient_terms
+        self.evaluator = evaluator
+        if len(self.writes) != num_quotient_terms:
+            raise ValueError("%d writes for %d quotient terms" % (len(self.writes), num_quotient_terms))
+
+
+def capture(evaluator):
+    """GPUDataCapture::from_evaluator (mod.rs:386-444)."""
+    ctx = TracingContext()
+    src, dst = TracingSource(ctx), TracingDestination()
+    shared = evaluator.load_row_shared_constants(src)
+    evaluator.evaluate_once(src, dst, shared)
+    return GateProgram(ctx.relations, dst.writes, evaluator.num_quotient_terms, evaluator)
+
+
+# ------------------------------------------------------------------ placement
+class PerChunkOffset:
+    """cs/traits/evaluator.rs PerChunkOffset."""
+
+    def __init__(self, variables_offset=0, witnesses_offset=0, constants_offset=0):
+        self.variables_offset = variables_offset
+        self.witnesses_offset = witnesses_offset
+        self.constants_offset = constants_offset
+
+    def as_tuple(self):
+        return (self.variables_offset, self.witnesses_offset, self.constants_offset)
+
+
+class CSGeometry:
+    def __init__(self, num_columns_under_copy_permutation, num_witness_columns, num_constant_columns,
+                 max_allowed_constraint_degree):
+        self.num_columns_under_copy_permutation = num_columns_under_copy_permutation
+        self.num_witness_columns = num_witness_columns
+        self.num_constant_columns = num_constant_columns
+        self.max_allowed_constraint_degree = max_allowed_constraint_degree
+
+
+class GatePlacement:
+    """One gate of a set.  selector_path: the list of booleans of compute_selector_subpath, level i
+    reading constant column i (empty: a selector of one).  constants_offset: where the gate's own
+    constants start -- len(selector_path) for a general-purpose gate, and for a specialized one the
+    constants of the general-purpose set (initial_offset's constants are added on top)."""
+
+    def __init__(self, program, num_repetitions=1, per_chunk_offset=None, selector_path=(), constants_offset=None,
+                 initial_offset=None):
+        self.program = program
+        self.num_repetitions = int(num_repetitions)
+        if per_chunk_offset is None:
+            per_chunk_offset = program.evaluator.per_chunk_offset if program.evaluator else PerChunkOffset()
+        self.per_chunk_offset = per_chunk_offset
+        self.selector_path = [bool(b) for b in selector_path]
+        self.constants_offset = len(self.selector_path) if constants_offset is None else int(constants_offset)
+        self.initial_offset = initial_offset or PerChunkOffset()
+
+    def bases(self):
+        v, w, c = self.initial_offset.as_tuple()
+        return (v, w, self.constants_offset + c)
+
+    def num_terms(self):
+        return self.num_repetitions * self.program.num_quotient_terms
+
+
+def layout_general_purpose(evaluators_with_paths, geometry):
+    """The general-purpose gates of a set: (evaluator, selector path) pairs in evaluation order ->
+    placements with the geometry's repetition counts and constants_offset = len(path)
+    (prover.rs:996-1015)."""
+    return [GatePlacement(capture(e), e.num_repetitions_in_geometry(geometry), e.per_chunk_offset, path)
+            for e, path in evaluators_with_paths]
+
+
+def specialized_placement(evaluator, num_repetitions, share_constants, initial_offset,
+                          constants_for_gates_over_general_purpose_columns):
+    """GatePlacementStrategy::UseSpecializedColumns (prover.rs:692-772): no selector, the source
+    narrowed to the columns from initial_offset on, the constants after the general-purpose ones;
+    with share_constants the repetitions do not advance the constants (:750-752)."""
+    v, w, c = evaluator.principal_width
+    per = PerChunkOffset(v, w, 0 if share_constants else c)
+    return GatePlacement(capture(evaluator), num_repetitions, per, (),
+                         constants_for_gates_over_general_purpose_columns, initial_offset)
+
+
+# ------------------------------------------------------------------ slot allocation and the image
+_OPCODE = {k: i for i, k in enumerate(_RELATIONS)}
+_KIND_CODE = {"VariablePoly": 0, "WitnessPoly": 1, "ConstantPoly": 2}
+_K_SLOT, _K_IMM, _IDX_BITS = 3, 4, 21
+
+
+def allocate_slots(program, cap=MAX_SLOTS):
+    """Liveness analysis and slot reuse: TemporaryValue index -> slot, for every relation in order.
+    A temporary is live from the relation that defines it to its last read; one that is pushed to
+    the destination stays live to the end, because the terms are formed after the program has run.
+    An instruction reads its operands before it writes, so its destination may take the slot of an
+    operand that dies there.  Returns (slots, used): slots[i] the slot of relation i's destination,
+    used the number of distinct slots.  ValueError when more than cap values are live at once, or a
+    temporary is read before it is defined."""
+    end = len(program.relations)
+    last = {}
+    defined = set()
+    for i, (dst, rel) in enumerate(program.relations):
+        for o in rel.operands:
+            if o.kind == "TemporaryValue":
+                if o.value not in defined:
+                    raise ValueError("TemporaryValue(%d) is read before it is written" % o.value)
+                last[o.value] = i
+        if dst in defined:
+            raise ValueError("TemporaryValue(%d) is written twice" % dst)
+        defined.add(dst)
+    for o in program.writes:
+        if o.kind == "TemporaryValue":
+            if o.value not in defined:
+                raise ValueError("TemporaryValue(%d) is pushed but never written" % o.value)
+            last[o.value] = end
+    free, slot_of, slots, used = [], {}, [], 0
+    for i, (dst, rel) in enumerate(program.relations):
+        for o in set(rel.operands):
+            if o.kind == "TemporaryValue" and last[o.value] == i:
+                free.append(slot_of[o.value])
+        if free:
+            s = min(free)
+            free.remove(s)
+        else:
+            s = used
+            used += 1
+            if used > cap:
+                raise ValueError("more than %d temporaries are live at relation %d" % (cap, i))
+        slot_of[dst] = s
+        slots.append(s)
+        if dst not in last:   # never read: dead at once
+            free.append(s)
+    return slots, used
+
+
+class _Segment:
+    def __init__(self, alpha_base):
+        self.alpha_base = alpha_base
+        self.desc, self.instr, self.writes, self.imm = [], [], [], []
+        self.imm_index = {}
+        self.terms = 0
+        self.depth = 0
+
+    def words(self):
+        head = [len(self.desc) // 8, len(self.instr), len(self.writes), len(self.imm), self.alpha_base, self.terms,
+                self.depth, 0]
+        return head + self.desc + self.instr + self.writes + self.imm
+
+
+def _encode_gate(seg, pl, cap):
+    """Appends one gate to a segment; returns False (segment untouched) when it does not fit."""
+    prog = pl.program
+    slots, _ = allocate_slots(prog, cap)
+    imm, imm_index = list(seg.imm), dict(seg.imm_index)
+    slot_of = {}
+
+    def operand(o):
+        if o.kind == "TemporaryValue":
+            return _K_SLOT << _IDX_BITS | slot_of[o.value]
+        if o.kind == "ConstantValue":
+            if o.value not in imm_index:
+                imm_index[o.value] = len(imm)
+                imm.append(o.value)
+            return _K_IMM << _IDX_BITS | imm_index[o.value]
+        if o.value >> _IDX_BITS:
+            raise ValueError("%r: index too large" % (o,))
+        return _KIND_CODE[o.kind] << _IDX_BITS | o.value
+
+    instr = []
+    for (dst, rel), s in zip(prog.relations, slots):
+        ops = [operand(o) for o in rel.operands]
+        slot_of[dst] = s
+        instr.append(_OPCODE[rel.kind] | s << 8 | ops[0] << 16 | (ops[1] << 40 if len(ops) > 1 else 0))
+    writes = [operand(o) for o in prog.writes]
+    if (len(seg.desc) // 8 + 1 > MAX_GATES or len(seg.instr) + len(instr) > MAX_INSTRUCTIONS
+            or len(seg.writes) + len(writes) > MAX_INSTRUCTIONS or len(imm) > MAX_INSTRUCTIONS):
+        return False
+    if len(pl.selector_path) > 63:
+        raise ValueError("selector path too long")
+    mask = sum(1 << i for i, b in enumerate(pl.selector_path) if b)
+    bases, per = pl.bases(), pl.per_chunk_offset.as_tuple()
+    i0, w0 = len(seg.instr), len(seg.writes)
+    seg.desc += [i0 | (i0 + len(instr)) << 32, w0 | (w0 + len(writes)) << 32,
+                 pl.num_repetitions | len(pl.selector_path) << 32, mask,
+                 bases[0] | per[0] << 32, bases[1] | per[1] << 32, bases[2] | per[2] << 32, 0]
+    seg.instr += instr
+    seg.writes += writes
+    seg.imm, seg.imm_index = imm, imm_index
+    seg.terms += pl.num_terms()
+    seg.depth = max(seg.depth, len(pl.selector_path))
+    return True
+
+
+def compile_gate_set(placements, slot_cap=MAX_SLOTS):
+    """Placements in evaluation order -> the upload image, a list of u64 words
+    (include/boojum_mi355x.h, "quotient gate terms").  Gates fill a segment until a cap of one launch
+    would be passed; the next segment's alpha base carries the challenge index on.  Host only."""
+    placements = list(placements)
+    if not placements:
+        raise ValueError("a gate set holds at least one gate with quotient terms")
+    segments, seg = [], _Segment(0)
+    for pl in placements:
+        if pl.program.num_quotient_terms == 0:
+            raise ValueError("a gate without quotient terms never reaches the library (prover.rs:922-994)")
+        if not _encode_gate(seg, pl, slot_cap):
+            if not seg.desc:
+                raise ValueError("one gate exceeds the caps of a launch")
+            segments.append(seg)
+            seg = _Segment(seg.alpha_base + seg.terms)
+            if not _encode_gate(seg, pl, slot_cap):
+                raise ValueError("one gate exceeds the caps of a launch")
+    segments.append(seg)
+    image = [MAGIC, len(segments)] + [0] * len(segments)
+    for i, s in enumerate(segments):
+        image[2 + i] = len(image)
+        image += s.words()
+    return image
+
+
+def check_image(image):
+    """bj_gate_set_check_h: the library's validator on a host image, no device.  Returns the dict
+    of what the image needs; raises BoojumError (BJ_EINVAL) for a malformed one."""
+    words = (ctypes.c_uint64 * len(image))(*image)
+    need = (ctypes.c_uint64 * 5)()
+    call("bj_gate_set_check_h", words, len(image), need)
+    return dict(variables=need[0], witnesses=need[1], constants=need[2], alphas=need[3], segments=need[4])
+
+
+class GateSet:
+    """Slot allocation, validation and the single upload of a gate set; keeps the device buffer
+    alive until it is collected or `release()`d.  `GateSet.from_image` uploads a prepared image."""
+
+    def __init__(self, placements, slot_cap=MAX_SLOTS):
+        self._handle = None
+        self._upload(compile_gate_set(placements, slot_cap))
+
+    @classmethod
+    def from_image(cls, image):
+        self = cls.__new__(cls)
+        self._handle = None
+        self._upload(list(image))
+        return self
+
+    def _upload(self, image):
+        self.image = image
+        self.need = check_image(image)
+        handle = ctypes.c_void_p()
+        call("bj_gate_set_upload_d", (ctypes.c_uint64 * len(image))(*image), len(image), ctypes.byref(handle))
+        self._handle = handle
+        self.num_segments = self.need["segments"]
+        self.num_terms = self.need["alphas"]
+
+    def release(self):
+        if self._handle is not None:
+            handle, self._handle = self._handle, None
+            load().bj_gate_set_release(handle)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _log2(n):
+    if n <= 0 or n & (n - 1):
+        raise ValueError("size must be a power of two, got %d" % n)
+    return n.bit_length() - 1
+
+
+def _lde(t, q, what):
+    """(data pointer, column stride, columns, n) of a (C, D, n) LDE, or zeros for None."""
+    if t is None:
+        return None, 0, 0, None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.int64, torch.uint64):
+        raise TypeError("%s: expected an int64 CUDA tensor of u64 field elements" % what)
+    if t.dim() != 3:
+        raise ValueError("%s: an LDE is (C, D, n)" % what)
+    c, d, n = t.shape
+    if d < q:
+        raise ValueError("%s: the LDE has %d cosets, the quotient degree is %d" % (what, d, q))
+    if t.stride(2) != 1 or (d > 1 and t.stride(1) != n):
+        raise ValueError("%s: the cosets of an LDE column must be contiguous" % what)
+    return t.data_ptr(), (t.stride(0) if c > 1 else d * n), c, n
+
+
+def challenges_tensor(alphas, device):
+    """Ext2 challenges [(c0, c1), ...] -> the (K, 2) device tensor the call reads."""
+    flat = [int(limb) % P for pair in alphas for limb in pair]
+    return to_device(np.array(flat, dtype=np.uint64).reshape(-1, 2), device)
+
+
+def evaluate_gate_terms(gate_set, variables_lde, witnesses_lde, constants_lde, alphas, quotient_degree, dst_c0,
+                        dst_c1):
+    """dst += the gate terms of every segment of gate_set (bj_quotient_gate_terms_d, one launch
+    each).  The LDEs are (C, D, n) tensors read in place at their first quotient_degree cosets;
+    one the set never names may be None.  alphas: the set's Ext2 challenge powers, a list of
+    (c0, c1) pairs (copied to the device here) or a (K, 2) device tensor (read in place, so a
+    captured graph sees later contents).  dst_c0, dst_c1: q * n words each."""
+    log_q = _log2(quotient_degree)
+    v, v_stride, n_v, n1 = _lde(variables_lde, quotient_degree, "variables_lde")
+    w, w_stride, n_w, n2 = _lde(witnesses_lde, quotient_degree, "witnesses_lde")
+    c, c_stride, n_c, n3 = _lde(constants_lde, quotient_degree, "constants_lde")
+    sizes = {n for n in (n1, n2, n3) if n is not None}
+    total = dst_c0.numel()
+    n = sizes.pop() if sizes else total // quotient_degree
+    if sizes or n * quotient_degree != total:
+        raise ValueError("the LDEs and the accumulator disagree on the domain size")
+    for d in (dst_c0, dst_c1):
+        if not d.is_cuda or d.dtype not in (torch.int64, torch.uint64) or d.numel() != total or not d.is_contiguous():
+            raise ValueError("an accumulator half holds q * n = %d contiguous words on the device" % total)
+    if not isinstance(alphas, torch.Tensor):
+        alphas = challenges_tensor(alphas, dst_c0.device)
+    if not alphas.is_cuda or alphas.dim() != 2 or alphas.shape[1] != 2 or not alphas.is_contiguous() \
+            or alphas.dtype not in (torch.int64, torch.uint64):
+        raise ValueError("alphas: a contiguous (K, 2) int64 device tensor")
+    for segment in range(gate_set.num_segments):
+        call("bj_quotient_gate_terms_d", gate_set._handle, segment, v, v_stride, n_v, w, w_stride, n_w, c, c_stride,
+             n_c, alphas.data_ptr(), alphas.shape[0], _log2(n), log_q, dst_c0.data_ptr(), dst_c1.data_ptr(),
+             stream_of(dst_c0))
+
+
+# ------------------------------------------------------------------ evaluators
+class Evaluator:
+    """What the library needs of a GateConstraintEvaluator: num_quotient_terms,
+    max_constraint_degree, the principal width (variables, witnesses, constants), placement_type's
+    per_chunk_offset, num_repetitions_in_geometry, num_required_constants_in_geometry,
+    load_row_shared_constants and evaluate_once.  Sources give field-likes with the TracingField
+    surface; src.field() gives one to draw constants from."""
+    name = ""
+    num_quotient_terms = 1
+    max_constraint_degree = 2
+    principal_width = (0, 0, 0)
+
+    @property
+    def per_chunk_offset(self):
+        """MultipleOnRow: the principal width in variables and witnesses, no constants."""
+        return PerChunkOffset(self.principal_width[0], self.principal_width[1], 0)
+
+    def num_repetitions_in_geometry(self, geometry):
+        return geometry.num_columns_under_copy_permutation // self.principal_width[0]
+
+    def num_required_constants_in_geometry(self, geometry):
+        return self.principal_width[2]
+
+    def load_row_shared_constants(self, src):
+        return ()
+
+    def evaluate_once(self, src, dst, shared):
+        raise NotImplementedError
+
+
+class FmaGateInBaseFieldWithoutConstant(Evaluator):
+    """c0 a b + c1 c - d (fma_gate_without_constant.rs:20-127): the two coefficients are row-shared
+    constants 0 and 1 (:81-93), the term is c1 c + c0 (a b) - d (:108-125)."""
+    name = "fma_gate_in_base_without_constant"
+    max_constraint_degree = 3
+    principal_width = (4, 0, 2)
+
+    def load_row_shared_constants(self, src):
+        return (src.get_constant_value(0), src.get_constant_value(1))
+
+    def evaluate_once(self, src, dst, shared):
+        a, b, c, d = (src.get_variable_value(i) for i in range(4))
+        quadratic, linear = shared
+        t = c.copy()
+        t.mul_assign(linear)
+        ab = a.copy()
+        ab.mul_assign(b)
+        t.mul_and_accumulate_into(quadratic, ab)
+        t.sub_assign(d)
+        dst.push_evaluation_result(t)
+
+
+class BooleanConstraintGate(Evaluator):
+    """a (1 - a) (boolean_allocator.rs:100-121)."""
+    name = "boolean_constraint"
+    principal_width = (1, 0, 0)
+
+    def evaluate_once(self, src, dst, shared):
+        a = src.get_variable_value(0)
+        t = src.field().one()
+        t.sub_assign(a)
+        r = a.copy()
+        r.mul_assign(t)
+        dst.push_evaluation_result(r)
+
+
+class ConstantsAllocatorGate(Evaluator):
+    """a - constant (constant_allocator.rs:107-126); every repetition has its own constant, so the
+    per-chunk offset advances the constants too (:54-62) and the repetitions are bounded by both
+    column counts (:65-73)."""
+    name = "constants_allocator"
+    max_constraint_degree = 1
+    principal_width = (1, 0, 1)
+
+    @property
+    def per_chunk_offset(self):
+        return PerChunkOffset(1, 0, 1)
+
+    def num_repetitions_in_geometry(self, geometry):
+        return min(geometry.num_constant_columns, geometry.num_columns_under_copy_permutation)
+
+    def num_required_constants_in_geometry(self, geometry):
+        return geometry.num_constant_columns
+
+    def evaluate_once(self, src, dst, shared):
+        r = src.get_variable_value(0)
+        r.sub_assign(src.get_constant_value(0))
+        dst.push_evaluation_result(r)
+
+
+class ReductionGate(Evaluator):
+    """sum_i var_i constant_i - result (reduction_gate.rs:103-126), N row-shared constants
+    (:91-100), N + 1 variables."""
+
+    def __init__(self, n=4):
+        self.n = n
+        self.name = "reduction_gate_%d" % n
+        self.principal_width = (n + 1, 0, n)
+
+    def load_row_shared_constants(self, src):
+        return tuple(src.get_constant_value(i) for i in range(self.n))
+
+    def evaluate_once(self, src, dst, shared):
+        r = src.field().zero()
+        for i in range(self.n):
+            r.mul_and_accumulate_into(src.get_variable_value(i), shared[i])
+        r.sub_assign(src.get_variable_value(self.n))
+        dst.push_evaluation_result(r)
+
+
+class SelectionGate(Evaluator):
+    """a s + (1 - s) b - result (selection_gate.rs:100-128)."""
+    name = "selection_gate"
+    principal_width = (4, 0, 0)
+
+    def evaluate_once(self, src, dst, shared):
+        a, b, s, result = (src.get_variable_value(i) for i in range(4))
+        r = a.copy()
+        r.mul_assign(s)
+        t = src.field().one()
+        t.sub_assign(s)
+        r.mul_and_accumulate_into(t, b)
+        r.sub_assign(result)
+        dst.push_evaluation_result(r)
+
+
+class ZeroCheckGate(Evaluator):
+    """Two terms (zero_check.rs:143-176): flag + input * inverse - 1 and input * flag.  The
+    inversion witness is variable 2, or witness column 0 when use_witness_column_for_inversion
+    (:158-162), which also changes the width and the repetition count (:50-114)."""
+    num_quotient_terms = 2
+
+    def __init__(self, use_witness_column_for_inversion=False):
+        self.use_witness_column_for_inversion = use_witness_column_for_inversion
+        self.name = "zero_check_%s" % ("witness" if use_witness_column_for_inversion else "variable")
+        self.principal_width = (2, 1, 0) if use_witness_column_for_inversion else (3, 0, 0)
+
+    def num_repetitions_in_geometry(self, geometry):
+        reps = geometry.num_columns_under_copy_permutation // self.principal_width[0]
+        if self.use_witness_column_for_inversion:
+            reps = min(reps, geometry.num_witness_columns)
+        return reps
+
+    def evaluate_once(self, src, dst, shared):
+        one = src.field().one()
+        inp, flag = src.get_variable_value(0), src.get_variable_value(1)
+        inv = src.get_witness_value(0) if self.use_witness_column_for_inversion else src.get_variable_value(2)
+        r = flag.copy()
+        r.mul_and_accumulate_into(inp, inv)
+        r.sub_assign(one)
+        dst.push_evaluation_result(r)
+        r = inp.copy()
+        r.mul_assign(flag)
+        dst.push_evaluation_result(r)
+
+
+class DotProductGate(Evaluator):
+    """sum_i a_i b_i - result over 2 N + 1 variables (dot_product_gate.rs:102-131)."""
+
+    def __init__(self, n=4):
+        self.n = n
+        self.name = "dot_product_gate_%d" % n
+        self.principal_width = (2 * n + 1, 0, 0)
+
+    def evaluate_once(self, src, dst, shared):
+        r = src.field().zero()
+        for i in range(self.n):
+            r.mul_and_accumulate_into(src.get_variable_value(2 * i), src.get_variable_value(2 * i + 1))
+        r.sub_assign(src.get_variable_value(2 * self.n))
+        dst.push_evaluation_result(r)
+
+
+class ConditionalSwapGate(Evaluator):
+    """2 N terms over 4 N + 1 variables (conditional_swap.rs:108-152): for each pair,
+    b s + (1 - s) a - result_a and a s + (1 - s) b - result_b, the selector being variable 0."""
+
+    def __init__(self, n=1):
+        self.n = n
+        self.name = "conditional_swap_gate_%d" % n
+        self.num_quotient_terms = 2 * n
+        self.principal_width = (4 * n + 1, 0, 0)
+
+    def evaluate_once(self, src, dst, shared):
+        s = src.get_variable_value(0)
+        for i in range(self.n):
+            a, b, ra, rb = (src.get_variable_value(4 * i + 1 + j) for j in range(4))
+            for taken, other, result in ((b, a, ra), (a, b, rb)):
+                r = taken.copy()
+                r.mul_assign(s)
+                t = src.field().one()
+                t.sub_assign(s)
+                r.mul_and_accumulate_into(t, other)
+                r.sub_assign(result)
+                dst.push_evaluation_result(r)
+
+
+def library():
+    """The evaluators of the library in a fixed order: eight gates, ZeroCheck in both placements."""
+    return [FmaGateInBaseFieldWithoutConstant(), BooleanConstraintGate(), ConstantsAllocatorGate(), ReductionGate(4),
+            SelectionGate(), ZeroCheckGate(False), ZeroCheckGate(True), DotProductGate(4), ConditionalSwapGate(1)]

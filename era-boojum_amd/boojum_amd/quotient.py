@@ -187,7 +187,7 @@ def quotient_monomials(dst_c0, dst_c1, log_n):
 
 
 def quotient_from_arguments(variables_lde, sigmas_lde, second_stage_lde, beta, gamma, challenges, quotient_degree,
-                            lookup=None, gate_terms=None):
+                            lookup=None, gate_terms=None, gates=None):
     """The block prover.rs:1145-1467 without the gate evaluation: accumulator (zeros, or the
     caller's gate terms (c0, c1), which are added to in place) -> copy-permutation terms -> lookup
     terms if any -> division -> monomials.  challenges: the Ext2 challenges in the reference's
@@ -196,6 +196,10 @@ def quotient_from_arguments(variables_lde, sigmas_lde, second_stage_lde, beta, g
     encodings).  lookup: None, or a dict with variables_lde (default: the variables_lde argument),
     multiplicities_lde, constants_lde, tables_lde, beta, gamma, table_id_column_idxes,
     column_elements_per_subargument, num_subarguments, variables_offset.
+    gates: None, or a dict with gate_set (a gates.GateSet), alphas (its Ext2 challenge powers),
+    constants_lde, and optionally witnesses_lde and variables_lde (default: the variables_lde
+    argument): the gate terms are evaluated into the accumulator before the copy-permutation
+    terms (gates.evaluate_gate_terms); with gate_terms as well, both are added.
     Returns what quotient_monomials returns."""
     _, c, n, _ = _lde_view(variables_lde, quotient_degree)
     m = (c + quotient_degree - 1) // quotient_degree
@@ -205,6 +209,10 @@ def quotient_from_arguments(variables_lde, sigmas_lde, second_stage_lde, beta, g
         dst_c1 = torch.zeros_like(dst_c0)
     else:
         dst_c0, dst_c1 = gate_terms
+    if gates is not None:
+        from .gates import evaluate_gate_terms
+        evaluate_gate_terms(gates["gate_set"], gates.get("variables_lde", variables_lde), gates.get("witnesses_lde"),
+                            gates.get("constants_lde"), gates["alphas"], quotient_degree, dst_c0, dst_c1)
     challenges = list(challenges)
     compute_quotient_terms_in_extension(variables_lde, sigmas_lde, second_stage_lde, beta, gamma,
                                         challenges[:m + 1], quotient_degree, dst_c0, dst_c1)

@@ -1,0 +1,369 @@
+// Quotient gate terms: an evaluator of captured relation programs over LDE columns that stay on
+// the device (the loop prover.rs:560-1085 drives on the CPU).
+//
+// The circuit's evaluators stay the caller's.  What arrives here is what gpu_synthesizer/mod.rs
+// captures from an evaluator's evaluate_once: a straight-line program of Relation::{Add, Double,
+// Sub, Negate, Mul, Square} over Index::{VariablePoly, WitnessPoly, ConstantPoly, TemporaryValue,
+// ConstantValue} and the list of pushed terms, with its placement (repetitions, PerChunkOffset,
+// selector path, constants offset).  For every point L = coset * n + row of the first q cosets
+//   acc(L) += sum_gates selector_g(L) sum_rep sum_term alpha[k] term(L),
+// k running on across repetitions and gates: push_evaluation_result / proceed_to_next_gate /
+// advance (buffering_source.rs:157-221, 303-377), evaluate_over_general_purpose_columns
+// (cs/traits/evaluator.rs:376-397), compute_selector_subpath (prover.rs:2775-2916) and the
+// specialized-columns form, which has no selector (prover.rs:651-801).
+//
+// Kernel.  One point per lane, 256 lanes per workgroup, one launch for all gates of a segment; the
+// accumulator is read once and written once.  The program is wave-uniform: every word of it is
+// fetched through a uniform address of the uploaded image and forced into scalar registers
+// (readfirstlane), so the decode (field extracts, the operand-kind and opcode branches, the
+// column-address arithmetic) is scalar work and no lane takes a branch another does not.  A
+// temporary lives in an LDS slot laid out [slot][lane], 8 bytes per lane, so a wave's access is
+// 512 contiguous bytes: conflict free by construction, private to the lane, and no barrier is
+// needed.  The host allocates slots by liveness (boojum_amd/gates.py), so GT_SLOTS bounds the
+// values live at once, not the program's length.  The selector constants of a point (columns
+// 0 .. depth - 1) are loaded once into registers and every gate multiplies its own path from them.
+//
+// Image (u64 words, built by the caller, checked by check_image below, uploaded once):
+//   [0] GT_MAGIC  [1] number of segments S  [2 .. 2 + S) word offset of each segment
+//   segment: [0] gates G  [1] instructions I  [2] writes W  [3] immediates M  [4] alpha base
+//            [5] terms (sum over gates of repetitions * writes)  [6] selector columns read  [7] 0
+//            G descriptors of 8 words, I instructions, W writes, M immediates
+//   descriptor: [0] instr begin | end << 32   [1] write begin | end << 32
+//               [2] repetitions | path length << 32   [3] path bit mask (bit i set: take column i,
+//               clear: 1 - column i)   [4] variables base | per repetition << 32
+//               [5] witnesses base | per repetition << 32   [6] constants base | per repetition << 32
+//               [7] 0
+//   instruction: opcode | slot << 8 | a << 16 | b << 40;  operand (24 bits): kind << 21 | index
+//   kinds: 0 VariablePoly, 1 WitnessPoly, 2 ConstantPoly, 3 slot, 4 immediate (index into M)
+//   opcodes: Relation's order -- 0 Add, 1 Double, 2 Sub, 3 Negate, 4 Mul, 5 Square; 6 Inverse is
+//   refused.  No evaluator in cs/gates records it: the three textual hits
+//   (fma_gate_without_constant.rs:353, fma_gate_in_extension_without_constant.rs:451,
+//   zero_check.rs:539) are all inside witness-resolution closures, not evaluate_once.
+//
+// One call launches one segment.  A gate set over the caps is split into segments by the caller,
+// which is exact because the call adds to the accumulator and a segment carries its alpha base.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <new>
+#include "gl.hpp"
+#include "bj_internal.hpp"
+#include "../../include/boojum_mi355x.h"
+
+namespace bj {
+
+namespace {
+
+constexpr uint64_t GT_MAGIC = 0x3153455441474A42ULL;  // "BJGATES1"
+constexpr uint32_t GT_THREADS = 256;
+constexpr uint32_t GT_SLOTS = BJ_GATE_MAX_SLOTS;        // 16 slots of 2 KB: 32 KB, five workgroups per CU
+constexpr uint32_t GT_SEL = BJ_GATE_MAX_SELECTOR_DEPTH;
+constexpr uint32_t GT_INSTRS = BJ_GATE_MAX_INSTRUCTIONS;
+constexpr uint32_t GT_GATES = BJ_GATE_MAX_GATES;
+constexpr uint32_t GT_HDR = 8, GT_DESC = 8;
+constexpr uint32_t K_VAR = 0, K_WIT = 1, K_CONST = 2, K_SLOT = 3, K_IMM = 4;
+constexpr uint32_t OP_ADD = 0, OP_DOUBLE = 1, OP_SUB = 2, OP_NEGATE = 3, OP_MUL = 4, OP_SQUARE = 5;
+static_assert(OP_ADD == 0 && OP_SUB == 2 && OP_MUL == 4, "Relation's order (gpu_synthesizer/mod.rs:125-133)");
+constexpr uint32_t IDX_BITS = 21, IDX_MASK = (1u << IDX_BITS) - 1;
+
+struct Cols {
+    const uint64_t* p[3];  // variables, witnesses, constants: coset 0 of column 0
+    size_t stride[3];
+};
+
+// a uniform word of the image, in scalar registers
+__device__ __forceinline__ uint64_t uword(const uint64_t* __restrict__ p) {
+    const uint64_t v = *p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__device__ __forceinline__ uint64_t fetch(uint32_t operand, const Cols& cols, const uint32_t (&off)[3], size_t L,
+                                          const uint64_t* slots, const uint64_t* __restrict__ imm) {
+    const uint32_t kind = operand >> IDX_BITS, idx = operand & IDX_MASK;
+    if (kind == K_SLOT) return slots[idx * GT_THREADS];
+    if (kind == K_IMM) return uword(imm + idx);
+    if (kind == K_VAR) return cols.p[0][(size_t)(idx + off[0]) * cols.stride[0] + L];
+    if (kind == K_WIT) return cols.p[1][(size_t)(idx + off[1]) * cols.stride[1] + L];
+    return cols.p[2][(size_t)(idx + off[2]) * cols.stride[2] + L];
+}
+
+__global__ __launch_bounds__(GT_THREADS) void gate_terms_kernel(const uint64_t* __restrict__ seg, Cols cols,
+                                                                const uint64_t* __restrict__ alphas, size_t total,
+                                                                uint64_t* __restrict__ dst0,
+                                                                uint64_t* __restrict__ dst1) {
+    __shared__ uint64_t lds[GT_SLOTS * GT_THREADS];
+    uint64_t* slots = lds + threadIdx.x;
+    const size_t l = blockIdx.x * (size_t)GT_THREADS + threadIdx.x;
+    const bool in = l < total;
+    const size_t L = in ? l : 0;  // a lane past the end reads point 0 and writes nothing
+
+    const uint32_t n_gates = (uint32_t)uword(seg + 0), n_instr = (uint32_t)uword(seg + 1);
+    const uint32_t n_writes = (uint32_t)uword(seg + 2), sel_cols = (uint32_t)uword(seg + 6);
+    const uint64_t* __restrict__ desc = seg + GT_HDR;
+    const uint64_t* __restrict__ instr = desc + (size_t)n_gates * GT_DESC;
+    const uint64_t* __restrict__ writes = instr + n_instr;
+    const uint64_t* __restrict__ imm = writes + n_writes;
+    const uint64_t* __restrict__ alpha = alphas + 2 * uword(seg + 4);
+
+    uint64_t selc[GT_SEL];
+#pragma unroll
+    for (uint32_t i = 0; i < GT_SEL; i++) selc[i] = i < sel_cols ? cols.p[2][(size_t)i * cols.stride[2] + L] : 0;
+
+    uint64_t acc0 = 0, acc1 = 0;
+    for (uint32_t g = 0; g < n_gates; g++) {
+        const uint64_t* __restrict__ d = desc + (size_t)g * GT_DESC;
+        const uint64_t d0 = uword(d), d1 = uword(d + 1), d2 = uword(d + 2), mask = uword(d + 3);
+        const uint64_t dv = uword(d + 4), dw = uword(d + 5), dc = uword(d + 6);
+        const uint32_t i0 = (uint32_t)d0, i1 = (uint32_t)(d0 >> 32), w0 = (uint32_t)d1, w1 = (uint32_t)(d1 >> 32);
+        const uint32_t reps = (uint32_t)d2, depth = (uint32_t)(d2 >> 32);
+        uint32_t off[3] = {(uint32_t)dv, (uint32_t)dw, (uint32_t)dc};
+        uint64_t g0 = 0, g1 = 0;
+        for (uint32_t rep = 0; rep < reps; rep++) {
+            for (uint32_t pc = i0; pc < i1; pc++) {
+                const uint64_t w = uword(instr + pc);
+                const uint32_t op = (uint32_t)w & 0xff, slot = (uint32_t)(w >> 8) & 0xff;
+                const uint64_t a = fetch((uint32_t)(w >> 16) & 0xffffff, cols, off, L, slots, imm);
+                uint64_t r;
+                if (op == OP_DOUBLE) {
+                    r = gl::add(a, a);
+                } else if (op == OP_NEGATE) {
+                    r = gl::sub(0, a);
+                } else if (op == OP_SQUARE) {
+                    r = gl::mul(a, a);
+                } else {
+                    const uint64_t b = fetch((uint32_t)(w >> 40) & 0xffffff, cols, off, L, slots, imm);
+                    r = op == OP_MUL ? gl::mul(a, b) : op == OP_ADD ? gl::add(a, b) : gl::sub(a, b);
+                }
+                slots[slot * GT_THREADS] = r;
+            }
+            for (uint32_t t = w0; t < w1; t++) {  // alpha_k * term: two base products
+                const uint64_t v = fetch((uint32_t)uword(writes + t) & 0xffffff, cols, off, L, slots, imm);
+                g0 = gl::add(g0, gl::mul(v, uword(alpha)));
+                g1 = gl::add(g1, gl::mul(v, uword(alpha + 1)));
+                alpha += 2;
+            }
+            off[0] += (uint32_t)(dv >> 32);
+            off[1] += (uint32_t)(dw >> 32);
+            off[2] += (uint32_t)(dc >> 32);
+        }
+        if (depth) {  // the selector multiplies the gate's sum once
+            uint64_t sel = 1;
+#pragma unroll
+            for (uint32_t i = 0; i < GT_SEL; i++) {
+                if (i < depth) {
+                    const uint64_t f = (mask >> i) & 1 ? selc[i] : gl::sub(1, selc[i]);
+                    sel = i == 0 ? f : gl::mul(sel, f);
+                }
+            }
+            g0 = gl::mul(g0, sel);
+            g1 = gl::mul(g1, sel);
+        }
+        acc0 = gl::add(acc0, g0);
+        acc1 = gl::add(acc1, g1);
+    }
+    if (in) {
+        dst0[L] = gl::canon(gl::add(acc0, dst0[L]));
+        dst1[L] = gl::canon(gl::add(acc1, dst1[L]));
+    }
+}
+
+// ------------------------------------------------------------------ host side: the image's checks
+struct Need {
+    uint64_t cols[3];  // columns the largest repetition reaches, per kind
+    uint64_t alphas;   // challenges the whole image consumes
+    uint64_t segments;
+};
+
+struct GateSet {
+    uint64_t magic;
+    uint64_t* image_d;
+    Need need;
+    uint64_t n_segments;
+    uint64_t seg_offset[BJ_GATE_MAX_SEGMENTS];
+};
+
+int bad(const char* why) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "gate program: %s", why);
+    return set_error(BJ_EINVAL, msg);
+}
+
+// An operand's claim on its space; false when it is outside.  written: the slots written so far.
+bool operand_ok(uint32_t operand, uint64_t n_imm, uint32_t written, const uint64_t (&last)[3], Need& need) {
+    const uint32_t kind = operand >> IDX_BITS, idx = operand & IDX_MASK;
+    if (kind == K_SLOT) return idx < GT_SLOTS && ((written >> idx) & 1);
+    if (kind == K_IMM) return idx < n_imm;
+    if (kind > K_IMM) return false;
+    const uint64_t reach = last[kind] + idx + 1;  // columns needed at the largest repetition
+    if (reach > ((uint64_t)1 << 31)) return false;
+    if (reach > need.cols[kind]) need.cols[kind] = reach;
+    return true;
+}
+
+int check_image(const uint64_t* image, size_t words, Need& need, uint64_t* seg_offset) {
+    need = Need{{0, 0, 0}, 0, 0};
+    if (!image) return bad("null image");
+    if (words < 2 || image[0] != GT_MAGIC) return bad("not a gate-set image");
+    const uint64_t n_seg = image[1];
+    if (n_seg == 0 || n_seg > BJ_GATE_MAX_SEGMENTS) return bad("segment count outside 1..BJ_GATE_MAX_SEGMENTS");
+    if (words < 2 + n_seg) return bad("truncated segment table");
+    need.segments = n_seg;
+    for (uint64_t s = 0; s < n_seg; s++) {
+        const uint64_t at = image[2 + s];
+        if (at < 2 + n_seg || at > words || words - at < GT_HDR) return bad("segment offset outside the image");
+        const uint64_t* seg = image + at;
+        const uint64_t G = seg[0], I = seg[1], W = seg[2], M = seg[3], base = seg[4], terms = seg[5], sel = seg[6];
+        if (G == 0 || G > GT_GATES) return bad("gates of a segment outside 1..BJ_GATE_MAX_GATES");
+        if (I > GT_INSTRS) return bad("a segment exceeds BJ_GATE_MAX_INSTRUCTIONS");
+        if (W > GT_INSTRS || M > GT_INSTRS) return bad("a segment's writes or immediates exceed BJ_GATE_MAX_INSTRUCTIONS");
+        if (words - at < GT_HDR + G * GT_DESC + I + W + M) return bad("truncated segment");
+        if (sel > GT_SEL) return bad("selector depth exceeds BJ_GATE_MAX_SELECTOR_DEPTH");
+        if (seg[7] != 0) return bad("reserved word is not zero");
+        if (base != need.alphas) return bad("a segment's alpha base is not the sum of the terms before it");
+        const uint64_t* desc = seg + GT_HDR;
+        const uint64_t* instr = desc + G * GT_DESC;
+        const uint64_t* writes = instr + I;
+        uint64_t count = 0, deepest = 0;
+        for (uint64_t g = 0; g < G; g++) {
+            const uint64_t* d = desc + g * GT_DESC;
+            const uint64_t i0 = d[0] & 0xffffffff, i1 = d[0] >> 32, w0 = d[1] & 0xffffffff, w1 = d[1] >> 32;
+            const uint64_t reps = d[2] & 0xffffffff, depth = d[2] >> 32;
+            if (i0 > i1 || i1 > I || w0 >= w1 || w1 > W) return bad("a gate's instruction or write range is malformed or has no terms");
+            if (reps == 0 || reps > (1u << 20)) return bad("num_repetitions outside 1..2^20");
+            if (depth > GT_SEL || (depth < 64 && (d[3] >> depth)) || d[7] != 0) return bad("malformed selector path");
+            if (depth > deepest) deepest = depth;
+            uint64_t last[3];
+            for (int k = 0; k < 3; k++) {
+                const uint64_t b = d[4 + k] & 0xffffffff, per = d[4 + k] >> 32;
+                if (b > (1u << 20) || per > (1u << 10)) return bad("a column offset is out of range");
+                last[k] = b + per * (reps - 1);
+            }
+            uint32_t written = 0;
+            for (uint64_t pc = i0; pc < i1; pc++) {
+                const uint64_t w = instr[pc];
+                const uint32_t op = (uint32_t)(w & 0xff), slot = (uint32_t)((w >> 8) & 0xff);
+                if (op == 6) return bad("Relation::Inverse is not evaluated (no evaluator in cs/gates records it)");
+                if (op > 6) return bad("unknown opcode");
+                if (slot >= GT_SLOTS) return bad("more temporaries live at once than BJ_GATE_MAX_SLOTS");
+                const bool unary = op == OP_DOUBLE || op == OP_NEGATE || op == OP_SQUARE;
+                if (!operand_ok((uint32_t)((w >> 16) & 0xffffff), M, written, last, need) ||
+                    (!unary && !operand_ok((uint32_t)((w >> 40) & 0xffffff), M, written, last, need)))
+                    return bad("an operand is outside its space, or a temporary is read before it is written");
+                if (unary && (w >> 40)) return bad("a unary relation carries a second operand");
+                written |= 1u << slot;
+            }
+            for (uint64_t t = w0; t < w1; t++) {
+                if (writes[t] >> 24 || !operand_ok((uint32_t)writes[t], M, written, last, need))
+                    return bad("a written operand is outside its space, or a temporary that was never written");
+            }
+            count += reps * (w1 - w0);
+        }
+        if (count != terms) return bad("a segment's term count is not the sum over its gates");
+        if (sel != deepest) return bad("a segment's selector columns are not its deepest path");
+        if (sel > need.cols[K_CONST]) need.cols[K_CONST] = sel;
+        need.alphas += terms;
+        if (seg_offset) seg_offset[s] = at;
+    }
+    return BJ_OK;
+}
+
+int hip_error(hipError_t e, const char* what) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
+    return set_error(BJ_EHIP, msg);
+}
+
+}  // namespace
+
+}  // namespace bj
+
+extern "C" {
+
+int bj_gate_set_check_h(const uint64_t* image, size_t words, uint64_t* need) {
+    bj::Need n;
+    if (const int rc = bj::check_image(image, words, n, nullptr)) return rc;
+    if (need) {
+        need[0] = n.cols[0], need[1] = n.cols[1], need[2] = n.cols[2];
+        need[3] = n.alphas, need[4] = n.segments;
+    }
+    return BJ_OK;
+}
+
+int bj_gate_set_upload_d(const uint64_t* image, size_t words, void** set) {
+    if (!set) return bj::set_error(BJ_EINVAL, "bj_gate_set_upload_d: null set");
+    *set = nullptr;
+    bj::GateSet* s = new (std::nothrow) bj::GateSet;
+    if (!s) return bj::set_error(BJ_EINVAL, "bj_gate_set_upload_d: out of host memory");
+    if (const int rc = bj::check_image(image, words, s->need, s->seg_offset)) {
+        delete s;
+        return rc;
+    }
+    s->magic = bj::GT_MAGIC;
+    s->n_segments = s->need.segments;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->image_d), words * sizeof(uint64_t));
+    if (e == hipSuccess) {
+        e = hipMemcpy(s->image_d, image, words * sizeof(uint64_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(s->image_d);
+    }
+    if (e != hipSuccess) {
+        delete s;
+        return bj::hip_error(e, "gate set upload");
+    }
+    *set = s;
+    return BJ_OK;
+}
+
+int bj_gate_set_release(void* set) {
+    bj::GateSet* s = static_cast<bj::GateSet*>(set);
+    if (!s) return BJ_OK;
+    if (s->magic != bj::GT_MAGIC) return bj::set_error(BJ_EINVAL, "bj_gate_set_release: not a gate set");
+    s->magic = 0;
+    const hipError_t e = hipFree(s->image_d);
+    delete s;
+    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "gate set release");
+}
+
+int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* vars, size_t vars_stride,
+                             uint32_t n_vars, const uint64_t* wits, size_t wits_stride, uint32_t n_wits,
+                             const uint64_t* consts, size_t consts_stride, uint32_t n_consts, const uint64_t* alphas,
+                             uint32_t n_alphas, uint32_t log_n, uint32_t log_q, uint64_t* dst0, uint64_t* dst1,
+                             void* stream) {
+    const bj::GateSet* s = static_cast<const bj::GateSet*>(set);
+    if (!s || s->magic != bj::GT_MAGIC) return bj::set_error(BJ_EINVAL, "bj_quotient_gate_terms_d: not a gate set");
+    if (log_n > 32 || log_q > 32 || log_n + log_q > 32)
+        return bj::set_error(BJ_EINVAL, "log_n + log_q exceeds the 2-adicity (32) of the field");
+    if (segment >= s->n_segments) return bj::set_error(BJ_EINVAL, "bj_quotient_gate_terms_d: no such segment");
+    if (!alphas || !dst0 || !dst1) return bj::set_error(BJ_EINVAL, "bj_quotient_gate_terms_d: null pointer");
+    const size_t total = (size_t)1 << (log_n + log_q);
+    const uint64_t* p[3] = {vars, wits, consts};
+    const size_t stride[3] = {vars_stride, wits_stride, consts_stride};
+    const uint32_t have[3] = {n_vars, n_wits, n_consts};
+    static const char* const name[3] = {"variables", "witnesses", "constants"};
+    bj::Cols cols;
+    for (int k = 0; k < 3; k++) {
+        char msg[160];
+        if (s->need.cols[k] > have[k]) {
+            snprintf(msg, sizeof msg, "gate program: an operand reaches %s column %llu of %u", name[k],
+                     (unsigned long long)(s->need.cols[k] - 1), have[k]);
+            return bj::set_error(BJ_EINVAL, msg);
+        }
+        if (s->need.cols[k] && (!p[k] || stride[k] < total)) {
+            snprintf(msg, sizeof msg, "bj_quotient_gate_terms_d: %s are null or their stride is below 2^(log_n + log_q)",
+                     name[k]);
+            return bj::set_error(BJ_EINVAL, msg);
+        }
+        // a kind no operand names is never read; point it at the accumulator so no lane forms a null address
+        cols.p[k] = s->need.cols[k] ? p[k] : dst0;
+        cols.stride[k] = s->need.cols[k] ? stride[k] : 0;
+    }
+    if (s->need.alphas > n_alphas) return bj::set_error(BJ_EINVAL, "gate program: fewer challenges than terms");
+    const size_t blocks = (total + bj::GT_THREADS - 1) / bj::GT_THREADS;
+    hipLaunchKernelGGL(bj::gate_terms_kernel, dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream), s->image_d + s->seg_offset[segment], cols, alphas, total,
+                       dst0, dst1);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "quotient gate terms");
+}
+
+}  // extern "C"

@@ -659,6 +659,85 @@ int bj_quotient_divide_vanishing_d(uint64_t* dst0, uint64_t* dst1, uint32_t log_
  * BJ_EINVAL: log_n + log_q > 32, null out. */
 int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out);
 
+/* ------------------------------------------------------------------ quotient gate terms */
+/* The gate terms of the quotient (the loop prover.rs:560-1085 drives on the CPU) for gates given
+ * as captured programs.  The evaluators stay the caller's: what arrives is what
+ * gpu_synthesizer/mod.rs records from evaluate_once -- relations Relation::{Add, Double, Sub,
+ * Negate, Mul, Square} over Index::{VariablePoly, WitnessPoly, ConstantPoly, TemporaryValue,
+ * ConstantValue}, and the operands pushed to the destination -- together with each gate's
+ * placement.  Added after 2.6; detect by symbol (bj_abi_version() is unchanged).  For every point
+ * L = coset * n + row of the first q cosets (the domain of the calls above)
+ *   dst[L] += sum_gates selector_g(L) sum_rep sum_term alpha[k] term(L),
+ * k running on across repetitions and gates and restarting per point
+ * (BufferedGateEvaluationReducingDestinationChunk::push_evaluation_result / proceed_to_next_gate /
+ * advance, buffering_source.rs:157-221, 303-377; evaluate_over_general_purpose_columns,
+ * cs/traits/evaluator.rs:376-397).  Terms are base-field values, a term times a challenge is two
+ * base products, the selector multiplies each gate's sum once, outputs are canonical.
+ * selector_g is the product over the gate's path of constant column i or 1 - column i
+ * (compute_selector_subpath, prover.rs:2775-2916); an empty path is 1, which is also the
+ * specialized-columns form (prover.rs:651-801).  ConstantPoly(j) of a gate reads constant column
+ * constants base + repetition * constants per repetition + j, the base being path length for a
+ * general-purpose gate and, for a specialized one, the constants of the general-purpose set plus
+ * the gate's initial offset.  A gate without quotient terms (NOP and marker gates,
+ * prover.rs:922-994) is not part of a set.
+ *
+ * The image (u64 words; INTEGRATION.md "Gate programs" describes how to build one from a capture):
+ *   [0] 0x3153455441474A42 ("BJGATES1")  [1] segments S  [2 .. 2 + S) word offset of each segment
+ *   segment:    [0] gates G  [1] instructions I  [2] writes W  [3] immediates M  [4] alpha base (the
+ *               terms of the segments before it)  [5] terms  [6] deepest selector path  [7] 0, then
+ *               G descriptors of 8 words, I instructions, W writes, M immediates
+ *   descriptor: [0] instruction begin | end << 32  [1] write begin | end << 32 (in push order)
+ *               [2] num_repetitions | path length << 32  [3] path mask, bit i set: column i, clear:
+ *               1 - column i  [4] variables base | per repetition << 32  [5] witnesses, [6]
+ *               constants likewise  [7] 0
+ *   instruction: opcode | destination slot << 8 | operand a << 16 | operand b << 40
+ *   operand (24 bits): kind << 21 | index; kinds 0 VariablePoly, 1 WitnessPoly, 2 ConstantPoly,
+ *               3 slot, 4 immediate (index into the segment's M words); a write is one operand
+ *   opcode:     0 Add, 1 Double, 2 Sub, 3 Negate, 4 Mul, 5 Square (Relation's order)
+ * A TemporaryValue lives in one of BJ_GATE_MAX_SLOTS slots per point; the caller assigns slots by
+ * liveness, so the cap bounds the values live at once (a pushed temporary stays live to the end of
+ * its program), not the program's length.  One call is one launch of one segment of at most
+ * BJ_GATE_MAX_GATES gates and BJ_GATE_MAX_INSTRUCTIONS instructions (and as many writes and
+ * immediates); a larger set is several segments and several calls, which is exact because every
+ * call adds to dst.
+ *
+ * Checks, all on the host and none per point: the magic, every range, the caps, an operand outside
+ * its space, a slot read before it is written in its gate, a term count or alpha base that does
+ * not add up, and opcode 6, Relation::Inverse.  No evaluator in cs/gates records Inverse: its three
+ * textual hits (fma_gate_without_constant.rs:353, fma_gate_in_extension_without_constant.rs:451,
+ * zero_check.rs:539) are inside witness-computation closures, not in evaluate_once. */
+#define BJ_GATE_MAX_SLOTS 16u
+#define BJ_GATE_MAX_SELECTOR_DEPTH 8u
+#define BJ_GATE_MAX_INSTRUCTIONS 4096u
+#define BJ_GATE_MAX_GATES 64u
+#define BJ_GATE_MAX_SEGMENTS 64u
+
+/* Validates a HOST image without touching a device.  need (5 words, may be NULL): the variable,
+ * witness and constant columns the largest repetition reaches (the selector columns included), the
+ * challenges the whole image consumes, the segments.  BJ_EINVAL as listed above. */
+int bj_gate_set_check_h(const uint64_t* image, size_t words, uint64_t* need);
+
+/* bj_gate_set_check_h, then the one upload: allocates words * 8 bytes on the current device, copies
+ * the image and synchronises.  *set is the handle the evaluation takes; it keeps the device buffer
+ * until bj_gate_set_release (NULL is a no-op).  On failure *set is NULL. */
+int bj_gate_set_upload_d(const uint64_t* image, size_t words, void** set);
+int bj_gate_set_release(void* set);
+
+/* dst += the gate terms of one segment of an uploaded set: one launch, no copy, no allocation and no
+ * synchronisation, so it captures into a HIP graph on `stream`.  vars, wits, consts: the LDE
+ * tensors of n_vars, n_wits, n_consts columns (coset 0 of column 0, columns `stride` words apart,
+ * D >= q as above), read in place; a kind the set never names may be NULL with count 0.  alphas:
+ * DEVICE array of n_alphas Ext2 challenges (c0, c1), the whole set's, indexed from the segment's
+ * alpha base.  dst0, dst1 are read once and written once per point.
+ * BJ_EINVAL (dst untouched): not a live handle, no such segment, log_n + log_q > 32, an operand
+ * that reaches a column index >= its count at the largest repetition, a stride below q * n,
+ * n_alphas below the set's terms, a null pointer that is read. */
+int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* vars, size_t vars_stride,
+                             uint32_t n_vars, const uint64_t* wits, size_t wits_stride, uint32_t n_wits,
+                             const uint64_t* consts, size_t consts_stride, uint32_t n_consts, const uint64_t* alphas,
+                             uint32_t n_alphas, uint32_t log_n, uint32_t log_q, uint64_t* dst0, uint64_t* dst1,
+                             void* stream);
+
 /* ------------------------------------------------------------------ queries */
 /* The query phase (prover.rs:2161-2266): every OracleQuery of a proof -- the leaf's elements
  * (QuerySource::get_elements, fri/mod.rs:683-927) and its Merkle path (get_proof,
