@@ -25,6 +25,9 @@ package is the host-side mirror of the reference's interface for that path:
                                                               buffering_source.rs:157-377, cs/gates/*.rs)
   queries  QueryOracle, construct_queries, OracleQuery, single_round_queries, fri_plan
                                                              (prover.rs:2161-2266, proof.rs:48-116)
+  fri      do_fri, FriOracles, fold_by, final_monomials, fold, interpolate
+                                                             (cs/implementations/fri/mod.rs:31-682)
+  transcript  Poseidon2Transcript                            (cs/implementations/transcript.rs:48-151)
   pow      PoWRunner, Blake2s256, Keccak256, NoPow, search  (cs/implementations/pow.rs, prover.rs:2107-2133)
 """
 from ._lib import BoojumError, load  # noqa: F401

@@ -97,6 +97,7 @@ SIGNATURES = {
     "bj_sharded_query_h": ([_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _int, _u64, _u64p, _u64p, _u64p,
                             _vp], _int),
     "bj_fri_fold_d": ([_vp, _vp, _sz, _vp, _u64, _u64, _u64, _vp, _vp, _vp], _int),
+    "bj_fri_fold_multi_d": ([_vp, _vp, _sz, _vp, _u64, _u64, _u64, _u32, _vp, _vp, _vp], _int),
     "bj_barycentric_weights_d": ([_u32, _u64, _u64, _u64, _vp, _vp, _vp], _int),
     "bj_evaluate_at_d": ([_vp, _u32, _sz, _u32, _vp, _vp, _vp, _vp], _int),
     "bj_deep_quotient_d": ([_vp, _u32, _sz, _vp, _u64, _u64, _u64, _u64, _u32, _sz, _sz, _vp, _vp, _int, _vp], _int),

@@ -9,10 +9,15 @@
 // full domain (precompute_twiddles_for_fft::<true>, fri/mod.rs:191-192). Over several cosets
 // stored one after another the root index is the flat pair index, which is what both
 // reference loops use. Outputs are canonical.
+//
+// bj_fri_fold_multi_d folds by 2^r (r = 1..3, the range do_fri allows, fri/mod.rs:204-205) in one
+// launch: the r by-2 steps of one reduction run on registers (fri_fold_multi_kernel).
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 #include "gl.hpp"
 #include "gl_asm.hpp"
 #include "bj_internal.hpp"
+#include "../../include/boojum_mi355x.h"
 
 namespace bj {
 
@@ -38,36 +43,113 @@ __device__ __forceinline__ ulonglong2 load_pair(const uint64_t* __restrict__ c, 
     return make_ulonglong2(c[2 * i], c[2 * i + 1]);
 }
 
+// One fold_multiple step on one pair of each column: (f(x), f(-x)) = (x0, y0) + (x1, y1) u and the
+// root r of the pair, beta and bsum in halves.  Canonical outputs.
+struct Beta {
+    uint32_t b0l, b0h, b1l, b1h, bsl, bsh;
+};
+__device__ __forceinline__ Beta beta_halves(uint64_t beta0, uint64_t beta1, uint64_t bsum) {
+    Beta b;
+    halves(beta0, b.b0l, b.b0h);
+    halves(beta1, b.b1l, b.b1h);
+    halves(bsum, b.bsl, b.bsh);
+    return b;
+}
+__device__ __forceinline__ void fold_pair(uint64_t x0, uint64_t y0, uint64_t x1, uint64_t y1, uint64_t r,
+                                          const Beta& b, uint64_t& o0, uint64_t& o1) {
+    uint32_t s0l, s0h, s1l, s1h, rl, rh;
+    halves(gl::sub(x0, y0), s0l, s0h);
+    halves(gl::sub(x1, y1), s1l, s1h);
+    halves(r, rl, rh);
+    uint32_t a0l, a0h, a1l, a1h;
+    glasm::mul_x2(s0l, s0h, rl, rh, a0l, a0h, s1l, s1h, rl, rh, a1l, a1h);
+    uint32_t sal, sah;
+    halves(gl::add(join(a0l, a0h), join(a1l, a1h)), sal, sah);
+    // (a0 + a1 u) (beta0 + beta1 u), u^2 = 7 (field/traits/field.rs:407-424)
+    uint32_t v0l, v0h, v1l, v1h, ml, mh;
+    glasm::mul_x3(a0l, a0h, b.b0l, b.b0h, v0l, v0h, a1l, a1h, b.b1l, b.b1h, v1l, v1h, sal, sah, b.bsl, b.bsh, ml,
+                  mh);
+    const uint64_t v0 = join(v0l, v0h), v1 = join(v1l, v1h);
+    const uint64_t e1 = gl::sub(gl::sub(join(ml, mh), v0), v1);
+    const uint64_t e0 = gl::add(v0, gl::sub(gl::mul_pow2_small(v1, 3), v1));  // v0 + 7 v1
+    o0 = gl::canon(gl::add(gl::add(e0, x0), y0));
+    o1 = gl::canon(gl::add(gl::add(e1, x1), y1));
+}
+
 template <bool V16>
 __global__ __launch_bounds__(256) void fri_fold_kernel(const uint64_t* __restrict__ c0,
                                                        const uint64_t* __restrict__ c1, size_t n_out,
                                                        const uint64_t* __restrict__ roots, uint64_t beta0,
                                                        uint64_t beta1, uint64_t bsum, uint64_t* __restrict__ d0,
                                                        uint64_t* __restrict__ d1) {
-    uint32_t b0l, b0h, b1l, b1h, bsl, bsh;
-    halves(beta0, b0l, b0h);
-    halves(beta1, b1l, b1h);
-    halves(bsum, bsl, bsh);
+    const Beta b = beta_halves(beta0, beta1, bsum);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_out; i += (size_t)gridDim.x * blockDim.x) {
         const ulonglong2 p0 = load_pair<V16>(c0, i), p1 = load_pair<V16>(c1, i);  // (f(x), f(-x))
-        const uint64_t r = roots[i];
-        uint32_t s0l, s0h, s1l, s1h, rl, rh;
-        halves(gl::sub(p0.x, p0.y), s0l, s0h);
-        halves(gl::sub(p1.x, p1.y), s1l, s1h);
-        halves(r, rl, rh);
-        uint32_t a0l, a0h, a1l, a1h;
-        glasm::mul_x2(s0l, s0h, rl, rh, a0l, a0h, s1l, s1h, rl, rh, a1l, a1h);
-        uint32_t sal, sah;
-        halves(gl::add(join(a0l, a0h), join(a1l, a1h)), sal, sah);
-        // (a0 + a1 u) (beta0 + beta1 u), u^2 = 7 (field/traits/field.rs:407-424)
-        uint32_t v0l, v0h, v1l, v1h, ml, mh;
-        glasm::mul_x3(a0l, a0h, b0l, b0h, v0l, v0h, a1l, a1h, b1l, b1h, v1l, v1h, sal, sah, bsl, bsh, ml, mh);
-        const uint64_t v0 = join(v0l, v0h), v1 = join(v1l, v1h);
-        const uint64_t e1 = gl::sub(gl::sub(join(ml, mh), v0), v1);
-        const uint64_t e0 = gl::add(v0, gl::sub(gl::mul_pow2_small(v1, 3), v1));  // v0 + 7 v1
-        d0[i] = gl::canon(gl::add(gl::add(e0, p0.x), p0.y));
-        d1[i] = gl::canon(gl::add(gl::add(e1, p1.x), p1.y));
+        uint64_t o0, o1;
+        fold_pair(p0.x, p0.y, p1.x, p1.y, roots[i], b, o0, o1);
+        d0[i] = o0;
+        d1[i] = o1;
     }
+}
+
+// Fold by 2^R in one pass: lane j holds the 2^R consecutive values [2^R j, 2^R (j + 1)) of each
+// column in registers and folds them R times.  Step s folds the 2^(R-1-s) pairs at flat index
+// i = 2^(R-1-s) j + t with roots[i] and beta_s = alpha^(2^s) coset_inverse^(2^s): exactly what R
+// by-2 passes compute (each step's outputs canonical, as the by-2 kernel stores them), without
+// the R - 1 round trips of the intermediate vectors.  Per output the pass moves 2 * 2^R values
+// in, 2^R - 1 roots in and 2 values out.  V16: both columns and the root table are 16-byte
+// aligned, so a lane's 2^R values (16, 32 or 64 bytes) and its root runs load as 16-byte words;
+// otherwise everything is 8-byte loads.
+struct FoldBetas {
+    uint64_t beta0[3], beta1[3], bsum[3];
+};
+
+template <int N, bool V16>
+__device__ __forceinline__ void load_run(const uint64_t* __restrict__ p, size_t first, uint64_t (&v)[8]) {
+    if constexpr (V16 && N >= 2) {
+        const ulonglong2* q = reinterpret_cast<const ulonglong2*>(p + first);  // first is a multiple of N
+#pragma unroll
+        for (int k = 0; k < N / 2; k++) {
+            const ulonglong2 w = q[k];
+            v[2 * k] = w.x;
+            v[2 * k + 1] = w.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) v[k] = p[first + k];
+    }
+}
+
+template <int R, bool V16>
+__global__ __launch_bounds__(256) void fri_fold_multi_kernel(const uint64_t* __restrict__ c0,
+                                                             const uint64_t* __restrict__ c1, size_t n_out,
+                                                             const uint64_t* __restrict__ roots, FoldBetas fb,
+                                                             uint64_t* __restrict__ d0,
+                                                             uint64_t* __restrict__ d1) {
+    static_assert(R >= 2 && R <= 3, "fold by 4 or 8");
+    const size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (j >= n_out) return;
+    constexpr int W = 1 << R;
+    uint64_t v0[8], v1[8], rt[3][8];
+    load_run<W, V16>(c0, j * W, v0);
+    load_run<W, V16>(c1, j * W, v1);
+    // the 2^R - 1 roots: the runs roots[2^(R-1) j ...], roots[2^(R-2) j ...], roots[j]
+    load_run<(W >> 1), V16>(roots, j * (W >> 1), rt[0]);
+    load_run<(W >> 2), V16>(roots, j * (W >> 2), rt[1]);
+    if constexpr (R == 3) load_run<1, V16>(roots, j, rt[2]);
+#pragma unroll
+    for (int s = 0; s < R; s++) {
+        const Beta b = beta_halves(fb.beta0[s], fb.beta1[s], fb.bsum[s]);
+#pragma unroll
+        for (int t = 0; t < (W >> (s + 1)); t++) {
+            uint64_t o0, o1;
+            fold_pair(v0[2 * t], v0[2 * t + 1], v1[2 * t], v1[2 * t + 1], rt[s][t], b, o0, o1);
+            v0[t] = o0;
+            v1[t] = o1;
+        }
+    }
+    d0[j] = v0[0];
+    d1[j] = v1[0];
 }
 
 }  // namespace
@@ -90,4 +172,72 @@ hipError_t launch_fri_fold(const uint64_t* c0, const uint64_t* c1, size_t n_out,
     return hipGetLastError();
 }
 
+namespace {
+
+// Step s of a fold by 2^r takes alpha^(2^s) (the challenge squared per step, fri/mod.rs:218-224)
+// and coset_inverse^(2^s) (squared after every fold, :554, :651); their product and its halves'
+// sum are folded here, on the host, as launch_fri_fold does for one step.
+FoldBetas fold_betas(uint64_t coset_inverse, uint64_t ch0, uint64_t ch1, uint32_t log_fold) {
+    FoldBetas fb = {};
+    uint64_t a0 = gl::canon(ch0), a1 = gl::canon(ch1), ci = gl::canon(coset_inverse);
+    for (uint32_t s = 0; s < log_fold; s++) {
+        fb.beta0[s] = gl::canon(gl::mul(a0, ci));
+        fb.beta1[s] = gl::canon(gl::mul(a1, ci));
+        fb.bsum[s] = gl::canon(gl::add(fb.beta0[s], fb.beta1[s]));
+        // (a0 + a1 u)^2 = a0^2 + 7 a1^2 + 2 a0 a1 u (field/traits/field.rs:427-440)
+        const uint64_t sq0 = gl::add(gl::mul(a0, a0), gl::mul(EXT2_NON_RESIDUE, gl::mul(a1, a1)));
+        const uint64_t sq1 = gl::mul(2, gl::mul(a0, a1));
+        a0 = gl::canon(sq0);
+        a1 = gl::canon(sq1);
+        ci = gl::canon(gl::mul(ci, ci));
+    }
+    return fb;
+}
+
+template <int R>
+hipError_t launch_fold_multi(const uint64_t* c0, const uint64_t* c1, size_t n_out, const uint64_t* roots,
+                             const FoldBetas& fb, uint64_t* d0, uint64_t* d1, hipStream_t st) {
+    const size_t blocks = (n_out + 255) / 256;  // one output per lane, no stride loop
+    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    if (((uintptr_t)c0 | (uintptr_t)c1 | (uintptr_t)roots) % 16 == 0)
+        hipLaunchKernelGGL((fri_fold_multi_kernel<R, true>), dim3((unsigned)blocks), dim3(256), 0, st, c0, c1, n_out,
+                           roots, fb, d0, d1);
+    else
+        hipLaunchKernelGGL((fri_fold_multi_kernel<R, false>), dim3((unsigned)blocks), dim3(256), 0, st, c0, c1, n_out,
+                           roots, fb, d0, d1);
+    return hipGetLastError();
+}
+
+}  // namespace
+
 }  // namespace bj
+
+extern "C" {
+
+int bj_fri_fold_multi_d(const uint64_t* c0, const uint64_t* c1, size_t n_src, const uint64_t* roots,
+                        uint64_t coset_inverse, uint64_t ch0, uint64_t ch1, uint32_t log_fold, uint64_t* dst_c0,
+                        uint64_t* dst_c1, void* stream) {
+    if (log_fold < 1 || log_fold > 3) return bj::set_error(BJ_EINVAL, "bj_fri_fold_multi_d: log_fold outside 1..3");
+    if (n_src & (((size_t)1 << log_fold) - 1))
+        return bj::set_error(BJ_EINVAL, "bj_fri_fold_multi_d: n_src is no multiple of 2^log_fold");
+    if (n_src == 0) return BJ_OK;
+    if (!c0 || !c1 || !roots || !dst_c0 || !dst_c1) return bj::set_error(BJ_EINVAL, "bj_fri_fold_multi_d: null pointer");
+    if (((uintptr_t)c0 | (uintptr_t)c1 | (uintptr_t)roots | (uintptr_t)dst_c0 | (uintptr_t)dst_c1) % 8)
+        return bj::set_error(BJ_EINVAL, "bj_fri_fold_multi_d: a pointer is not 8-byte aligned");
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t n_out = n_src >> log_fold;
+    hipError_t e;
+    if (log_fold == 1) {
+        e = bj::launch_fri_fold(c0, c1, n_out, roots, coset_inverse, ch0, ch1, dst_c0, dst_c1, st);
+    } else {
+        const bj::FoldBetas fb = bj::fold_betas(coset_inverse, ch0, ch1, log_fold);
+        e = log_fold == 2 ? bj::launch_fold_multi<2>(c0, c1, n_out, roots, fb, dst_c0, dst_c1, st)
+                          : bj::launch_fold_multi<3>(c0, c1, n_out, roots, fb, dst_c0, dst_c1, st);
+    }
+    if (e == hipSuccess) return BJ_OK;
+    char msg[160];
+    snprintf(msg, sizeof msg, "fri fold by 2^%u: %s", log_fold, hipGetErrorString(e));
+    return bj::set_error(BJ_EHIP, msg);
+}
+
+}  // extern "C"

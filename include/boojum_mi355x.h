@@ -473,6 +473,28 @@ int bj_fri_fold_d(const uint64_t* c0, const uint64_t* c1, size_t n_src, const ui
                   uint64_t coset_inverse, uint64_t ch0, uint64_t ch1, uint64_t* dst_c0, uint64_t* dst_c1,
                   void* stream);
 
+/* One FRI reduction step, a fold by 2^log_fold (log_fold = 1, 2 or 3, the range do_fri allows,
+ * fri/mod.rs:204-205), in one launch.  Added after 2.6; detect by symbol (bj_abi_version() is
+ * unchanged).  dst_j, j < n_src / 2^log_fold, is the result of log_fold successive fold_multiple
+ * steps over the 2^log_fold consecutive values [2^log_fold j, 2^log_fold (j + 1)) of each column.
+ * Step s = 0 .. log_fold - 1 folds the pairs at flat index i = 2^(log_fold-1-s) j + t with
+ * roots[i], the challenge alpha^(2^s) (squared per step, fri/mod.rs:218-224) and
+ * coset_inverse^(2^s) (:554, :651): bit for bit what log_fold calls of bj_fri_fold_d give when
+ * the caller squares the challenge and the coset inverse between them, for any u64 inputs.
+ * One output per lane with the 2^log_fold inputs of each column in registers, so the
+ * intermediate vectors never reach memory: 2 * 2^log_fold values and 2^log_fold - 1 roots in and
+ * 2 values out per output.  c0, c1 and roots at 16-byte-aligned addresses load a lane's values as
+ * 16-byte words (16, 32 or 64 contiguous bytes per column); any other 8-byte-aligned address
+ * runs the same fold with 8-byte loads.  roots holds at least n_src / 2 entries, as for
+ * bj_fri_fold_d.  dst_c0 / dst_c1 must not overlap c0, c1 or roots.  Outputs canonical; alpha
+ * travels by value, so the call can be captured in a HIP graph.
+ * BJ_EINVAL: log_fold 0 or > 3, n_src no multiple of 2^log_fold, a null pointer or one that is
+ * not 8-byte aligned (with n_src > 0).  n_src = 0 succeeds and touches nothing.  log_fold = 1
+ * runs bj_fri_fold_d's kernel. */
+int bj_fri_fold_multi_d(const uint64_t* c0, const uint64_t* c1, size_t n_src, const uint64_t* roots,
+                        uint64_t coset_inverse, uint64_t ch0, uint64_t ch1, uint32_t log_fold,
+                        uint64_t* dst_c0, uint64_t* dst_c1, void* stream);
+
 /* ------------------------------------------------------------------ DEEP */
 /* Evaluations at the out-of-domain point z and the quotening pass that builds the codeword
  * bj_fri_fold_d folds, on LDE columns that stay on the device.  Added after 2.6; detect by symbol
