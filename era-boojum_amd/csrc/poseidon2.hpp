@@ -16,7 +16,8 @@
 //   4-instruction reduction (glasm::reduce_xN) turns (L, H) back into a u64 per element;
 // * a full round's constant is one 64-bit add into L (the reduction takes any L < 2^64 - 2^40
 //   plus H < 2^40); a partial round's constant costs nothing or one add per limb (Sched);
-// * S-box multiplies are the interleaved inline-asm products of gl_asm.hpp.
+// * S-box multiplies are the interleaved inline-asm products of gl_asm.hpp; a full round's last
+//   product per element stays unreduced and goes to the external MDS as limbs (sched, below).
 #pragma once
 #include "gl.hpp"
 #include "gl_asm.hpp"
@@ -49,7 +50,8 @@ __device__ __constant__ static const RcLimbs RCL = make_rc_limbs();
 // ---- The constant schedule (field values; every entry canonical, computed at compile time) ----
 //
 // The reference adds RC_r before round r's S-boxes (state_generic_impl.rs:131-138, 55-64).
-// * Full rounds: the limbs after an external MDS are L, H < 2^39; L + RC_r stays below
+// * Full rounds: the limbs after an external MDS are L < 2^40, H < 2^39 (from 32-bit words
+//   both < 2^38; from a lazy full round's limbs, see LAZY_OFF below); L + RC_r stays below
 //   2^64 - 2^40 for every full-round constant (checked below), where the reduction is still
 //   exact (reduce_stream: W = Hhi EPS + L < 2^64), so RC_r is one 64-bit add into L instead of
 //   a 32-bit limb add into each of L and H.
@@ -69,7 +71,7 @@ constexpr uint64_t addm(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned _
 constexpr uint64_t subm(uint64_t a, uint64_t b) { return addm(a, P - b % P); }
 constexpr uint64_t mulm(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a * b) % P); }
 constexpr int SH[12] = {4, 14, 11, 8, 0, 5, 2, 9, 13, 6, 3, 12};
-// A 64-bit constant added into L: L < 2^39 after an external MDS, so L + c < 2^64 - 2^40
+// A 64-bit constant added into L: L < 2^40 after an external MDS, so L + c < 2^64 - 2^40
 // whenever c < 2^64 - 2^41.
 constexpr uint64_t FULL_RC_BOUND = ~0ull - (1ull << 41) + 1;
 // After the last partial round L < 2^60.1 and H < 2^61.1 (mi_layer_b_limbs on mi_layer_a_g's limbs,
@@ -112,6 +114,40 @@ constexpr bool full_rcs_fit() {
     return RC_FLAT[4][0] < FULL_RC_BOUND;
 }
 static_assert(full_rcs_fit(), "a full-round constant is too large for the one-add form");
+
+// ---- The lazy S-box hand-off (full rounds) ----
+//
+// A full round's last S-box product is not reduced: glasm::mul_lazy_x4 hands the external MDS
+// two 64-bit limbs per element, Lin + Hin 2^32 - LAZY_OFF == x^7 (mod p) with
+// Lin <= 3 (2^32 - 1) and Hin <= 2 (2^32 - 1).  The MDS is linear with non-negative
+// coefficients whose rows sum to 64 (even outputs) or 48 (odd ones) in every output form, so
+// after it L < 3 * 2^38 < 2^40, H < 2^39, and element i carries the offset
+// lazy_off(i) = me_row_sum(i) * LAZY_OFF <= 2^39 - 128.  The next round's one 64-bit add takes
+// it out: L += RC - lazy_off(i), non-negative for every constant of the table (checked below),
+// and W = Hhi EPS + L + c < 2^39 + 3 * 2^38 + c < 2^64 for c < FULL_RC_BOUND, as before.
+// Where no constant follows (elements 1..11 entering the partial rounds, the outputs of the
+// last round) L - lazy_off(i) may be negative, so the offset leaves as
+// -rs LAZY_OFF == p - 2 rs (2^32 - 1) = (EPS - 2 rs) 2^32 + (1 + 2 rs): one small add into each
+// of L and H (H < 2^39 + 2^32).
+constexpr uint64_t LAZY_OFF = 2 * 0xFFFFFFFFull;
+constexpr uint64_t me_row_sum(int i) { return (i & 1) ? 48 : 64; }
+constexpr uint64_t lazy_off(int i) { return me_row_sum(i) * LAZY_OFF; }
+constexpr uint64_t lazy_fix_lo(int i) { return 1 + 2 * me_row_sum(i); }
+constexpr uint64_t lazy_fix_hi(int i) { return 0xFFFFFFFFull - 2 * me_row_sum(i); }
+// the rounds whose incoming limbs come from a lazy full round (round 4: element 0 only)
+constexpr bool lazy_in(int r) { return (r >= 1 && r <= 3) || (r >= 27 && r <= 29); }
+constexpr bool lazy_rcs_fit() {
+    for (int r = 0; r < 30; r++)
+        for (int i = 0; i < 12; i++)
+            if ((lazy_in(r) || (r == 4 && i == 0)) &&
+                (RC_FLAT[r][i] < lazy_off(i) || RC_FLAT[r][i] - lazy_off(i) >= FULL_RC_BOUND))
+                return false;
+    return true;
+}
+static_assert(lazy_rcs_fit(), "a full-round constant is smaller than the lazy offset it takes out");
+static_assert((lazy_fix_lo(0) + (lazy_fix_hi(0) << 32) + lazy_off(0)) == P &&
+                  (lazy_fix_lo(1) + (lazy_fix_hi(1) << 32) + lazy_off(1)) == P,
+              "the two-limb form of -lazy_off");
 }  // namespace sched
 
 // The schedule's device tables: full words, and (value, 0) limb pairs for the asm layers.
@@ -125,11 +161,21 @@ struct Sched {
     uint64_t k_lo[11], k_hi[11];
     uint64_t d_lo[10], d_hi[10];
     uint64_t rc26_w[12], rc26_lo[12], rc26_hi[12];
+    // the full rounds' one-add constants as the rounds take them: RC_r - lazy_off where the
+    // incoming limbs come from a lazy full round (rounds 1..3, 27..29, and RC_4[0]), RC_r
+    // elsewhere; split 8 + 4 like rcw8 / rcw4, which stay as the plain table (the rounds read
+    // these)
+    uint64_t rcl8[30][8];
+    uint64_t rcl4[30][4];
 };
 constexpr Sched make_sched() {
     Sched s{};
     for (int r = 0; r < 30; r++)
-        for (int i = 0; i < 12; i++) (i < 8 ? s.rcw8[r][i] : s.rcw4[r][i - 8]) = RC_FLAT[r][i];
+        for (int i = 0; i < 12; i++) {
+            (i < 8 ? s.rcw8[r][i] : s.rcw4[r][i - 8]) = RC_FLAT[r][i];
+            const bool lazy = sched::lazy_in(r) || (r == 4 && i == 0);
+            (i < 8 ? s.rcl8[r][i] : s.rcl4[r][i - 8]) = RC_FLAT[r][i] - (lazy ? sched::lazy_off(i) : 0);
+        }
     for (int q = 0; q < 11; q++) { s.k_lo[q] = sched::V.k[q] & 0xFFFFFFFFull; s.k_hi[q] = sched::V.k[q] >> 32; }
     for (int q = 0; q < 10; q++) { s.d_lo[q] = sched::V.d[q] & 0xFFFFFFFFull; s.d_hi[q] = sched::V.d[q] >> 32; }
     for (int i = 0; i < 12; i++) {
@@ -145,8 +191,9 @@ struct State {
     uint32_t lo[12], hi[12];
 };
 
-// x^7 for 4 independent elements: x2 = x^2; x3 = x2*x, x4 = x2^2; x7 = x3*x4.
-__device__ __forceinline__ void sbox_x4(uint32_t* lo, uint32_t* hi) {
+// x^7 for 4 independent elements: x2 = x^2; x3 = x2*x, x4 = x2^2; x7 = x3*x4, the last product
+// handed on unreduced (sched, "lazy S-box hand-off"): Lin[j] + Hin[j] 2^32 - LAZY_OFF == x_j^7.
+__device__ __forceinline__ void sbox_lazy_x4(const uint32_t* lo, const uint32_t* hi, uint64_t* Lin, uint64_t* Hin) {
     uint32_t a0, a1, b0, b1, c0, c1, d0, d1;  // x2 of the four
     glasm::mul_x4(lo[0], hi[0], lo[0], hi[0], a0, a1, lo[1], hi[1], lo[1], hi[1], b0, b1,
                   lo[2], hi[2], lo[2], hi[2], c0, c1, lo[3], hi[3], lo[3], hi[3], d0, d1);
@@ -156,8 +203,8 @@ __device__ __forceinline__ void sbox_x4(uint32_t* lo, uint32_t* hi) {
     uint32_t i0, i1, j0, j1, k0, k1, l0, l1;  // x4 of the four
     glasm::mul_x4(a0, a1, a0, a1, i0, i1, b0, b1, b0, b1, j0, j1,
                   c0, c1, c0, c1, k0, k1, d0, d1, d0, d1, l0, l1);
-    glasm::mul_x4(e0, e1, i0, i1, lo[0], hi[0], f0, f1, j0, j1, lo[1], hi[1],
-                  g0, g1, k0, k1, lo[2], hi[2], h0, h1, l0, l1, lo[3], hi[3]);
+    glasm::mul_lazy_x4(e0, e1, i0, i1, Lin[0], Hin[0], f0, f1, j0, j1, Lin[1], Hin[1],
+                       g0, g1, k0, k1, Lin[2], Hin[2], h0, h1, l0, l1, Lin[3], Hin[3]);
 }
 
 __device__ __forceinline__ void sbox_x1(uint32_t& lo, uint32_t& hi) {
@@ -195,10 +242,10 @@ __device__ __forceinline__ uint64_t add_lo_u64(uint32_t lo, uint64_t b) {
 // last round's external MDS and the final reduction then form only those outputs.
 enum Out { OUT_ALL = 0, OUT_CAP = 1, OUT_DIGEST = 2 };
 
+// The external MDS on 64-bit limbs in place (inputs < 2^58: the coefficients of a row sum to
+// at most 64).  The lazy full rounds feed it mul_lazy_x4's limbs directly.
 template <int OUT = OUT_ALL>
-__device__ __forceinline__ void mds_ext_limbs(const uint32_t* v, uint64_t* X) {
-#pragma unroll
-    for (int i = 0; i < 12; i++) X[i] = v[i];
+__device__ __forceinline__ void mds_ext_limbs(uint64_t* X) {
     m4_limbs(X[0], X[1], X[2], X[3]);
     m4_limbs(X[4], X[5], X[6], X[7]);
     m4_limbs(X[8], X[9], X[10], X[11]);
@@ -216,6 +263,14 @@ __device__ __forceinline__ void mds_ext_limbs(const uint32_t* v, uint64_t* X) {
             X[i] = (a << 1) + b + c;
         }
     }
+}
+
+// The same from 32-bit words (zero-extended into limbs): the permutation's first MDS.
+template <int OUT = OUT_ALL>
+__device__ __forceinline__ void mds_ext_limbs(const uint32_t* v, uint64_t* X) {
+#pragma unroll
+    for (int i = 0; i < 12; i++) X[i] = v[i];
+    mds_ext_limbs<OUT>(X);
 }
 
 __device__ __forceinline__ void split(uint64_t z, uint32_t& lo, uint32_t& hi) {
@@ -243,19 +298,34 @@ __device__ __forceinline__ void reduce12(const uint64_t* L, const uint64_t* H, u
 }
 
 // Full round r on the pending limbs (L, H) of the state (the external MDS of the previous
-// step not yet reduced): reduce(L + RC_r, H) (Sched: one 64-bit add per element), x^7, then
-// the external MDS into new pending limbs.  Leaves the reduced S-box output in s.
+// step not yet reduced): reduce(L + c_r, H) (Sched::rcl8 / rcl4: one 64-bit add per element,
+// which also takes out the previous lazy round's offset), x^7 with the last product left as
+// limbs, then the external MDS on those limbs into new pending limbs, which carry
+// sched::lazy_off.  s holds the reduced S-box input only.
 template <int OUT = OUT_ALL, bool RC = true>
 __device__ __forceinline__ void full_round(State& s, uint64_t* L, uint64_t* H, int r) {
     if constexpr (RC) {
 #pragma unroll
-        for (int i = 0; i < 12; i++) L[i] += i < 8 ? SCH.rcw8[r][i] : SCH.rcw4[r][i - 8];
+        for (int i = 0; i < 12; i++) L[i] += i < 8 ? SCH.rcl8[r][i] : SCH.rcl4[r][i - 8];
     }
     reduce12(L, H, s.lo, s.hi);
 #pragma unroll
-    for (int q = 0; q < 3; q++) sbox_x4(s.lo + 4 * q, s.hi + 4 * q);
-    mds_ext_limbs<OUT>(s.lo, L);
-    mds_ext_limbs<OUT>(s.hi, H);
+    for (int q = 0; q < 3; q++) sbox_lazy_x4(s.lo + 4 * q, s.hi + 4 * q, L + 4 * q, H + 4 * q);
+    mds_ext_limbs<OUT>(L);
+    mds_ext_limbs<OUT>(H);
+}
+
+// Takes a lazy full round's offset out of element I's limbs where no round constant follows:
+// -lazy_off(I) == lazy_fix_lo(I) + lazy_fix_hi(I) 2^32 (mod p), both small and positive.
+template <int I>
+__device__ __forceinline__ void lazy_fix(uint64_t* L, uint64_t* H) {
+    L[I] += sched::lazy_fix_lo(I);
+    H[I] += sched::lazy_fix_hi(I);
+}
+template <int I, int N>
+__device__ __forceinline__ void lazy_fix_range(uint64_t* L, uint64_t* H) {
+    lazy_fix<I>(L, H);
+    if constexpr (I + 1 < N) lazy_fix_range<I + 1, N>(L, H);
 }
 
 // Two partial rounds (pair q: rounds 4 + 2q, 5 + 2q).  The state enters as element 0 reduced
@@ -337,7 +407,8 @@ __device__ __forceinline__ void permute(State& s) {
     mds_ext_limbs(s.hi, H);
 #pragma unroll 1
     for (int r = 0; r < 4; r++) full_round(s, L, H, r);
-    L[0] += SCH.rcw8[4][0];
+    L[0] += SCH.rcl8[4][0];  // RC_4[0] - lazy_off(0)
+    lazy_fix_range<1, 12>(L, H);
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         const int i = 4 * q;
@@ -358,6 +429,9 @@ __device__ __forceinline__ void permute(State& s) {
 #pragma unroll 1
     for (int r = 27; r < 29; r++) full_round(s, L, H, r);
     full_round<OUT>(s, L, H, 29);
+    if constexpr (OUT == OUT_ALL) lazy_fix_range<0, 12>(L, H);
+    else if constexpr (OUT == OUT_CAP) lazy_fix_range<8, 12>(L, H);
+    else lazy_fix_range<0, 4>(L, H);
     reduce12<OUT>(L, H, s.lo, s.hi);
 }
 

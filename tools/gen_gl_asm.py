@@ -76,6 +76,78 @@ def mul_stream(k, vbase, out=None):
     return I
 
 
+LAZY_OFFSET = 2 * 0xFFFFFFFF  # what mul_lazy's Lin carries above the product's low limb
+
+
+def mul_lazy_stream(k, vbase, ebase):
+    """a * b handed on unreduced, as two 64-bit limbs for a linear layer: 11 half-rate
+    instructions and one full-rate v_not_b32, against mul_stream's 14 plus the two moves that
+    zero-extend its result into limbs.  Returns (head, tail) instruction lists.
+
+    The four mads and the carry chain of mul_stream give the product's four 32-bit words
+    t0..t3 (t0 = P0, t1 = P1 + W0, t2 = W1 + V0 + c, t3 = V1 + cw + c').  With X = 2^32,
+    X^2 = X - 1 and X^3 = -1 (mod p):
+        a b = t0 + t1 X + t2 X^2 + t3 X^3 == (t0 - t2 - t3) + (t1 + t2) X,
+    so   Hin = t1 + t2                           (one mad; <= 2 (2^32 - 1) < 2^33)
+         Lin = t0 + ~t2 + ~t3                    (two mads; <= 3 (2^32 - 1) < 3 * 2^32)
+             = t0 - t2 - t3 + LAZY_OFFSET,
+    and Lin + Hin X - LAZY_OFFSET == a b (mod p) for any u64 a, b.  ~t3 comes out of the carry
+    chain itself: -1 - V1 - c' (v_subb_co_u32) is ~(V1 + c').  t2 is written into the low half
+    of a pair E whose high half the block's prologue zeroed, so (t2, 0) and then (~t2, 0) are
+    64-bit addends with no zero-extending move.  No step wraps: V1 + cw and V1 + c' are words of
+    a product < 2^128, and the mads add 32-bit words to values < 2^34.
+    Scratch pairs P, U, W, V at vbase..vbase+7, the E pair at ebase (shared by the streams whose
+    tails run one after the other); carries cA, cB, cW."""
+    P0, P1, U0, U1, W0, W1, V0, V1 = ["v%d" % (vbase + i) for i in range(8)]
+    P, U, W, V = ["v[%d:%d]" % (vbase + 2 * i, vbase + 2 * i + 1) for i in range(4)]
+    E0, E = "v%d" % ebase, "v[%d:%d]" % (ebase, ebase + 1)
+    cA, cB, cW = sp(3 * k), sp(3 * k + 1), sp(3 * k + 2)
+    a0, a1, b0, b1 = ["%%[%s%d]" % (n, k) for n in ("a0", "a1", "b0", "b1")]
+    Lin, Hin = "%%[Lin%d]" % k, "%%[Hin%d]" % k
+    head, tail = [], []
+    head.append(("v_mad_u64_u32 %s, %s, %s, %s, 0" % (U, JUNK, a1, b0), set(), {JUNK}))
+    head.append(("v_mad_u64_u32 %s, %s, %s, %s, 0" % (P, JUNK, a0, b0), set(), {JUNK}))
+    head.append(("v_mad_u64_u32 %s, %s, %s, %s, %s" % (W, cW, a0, b1, U), set(), {cW}))
+    head.append(("v_mad_u64_u32 %s, %s, %s, %s, 0" % (V, JUNK, a1, b1), set(), {JUNK}))
+    head.append(("v_add_co_u32 %s, %s, %s, %s" % (P1, cA, P1, W0), set(), {cA}))            # t1
+    head.append(("v_addc_co_u32 %s, %s, %s, 0, %s" % (V1, JUNK, V1, cW), {cW}, {JUNK}))     # V1 + cw
+    tail.append(("v_addc_co_u32 %s, %s, %s, %s, %s" % (E0, cB, W1, V0, cA), {cA}, {cB}))    # t2, c'
+    tail.append(("v_mad_u64_u32 %s, %s, %s, 1, %s" % (Hin, JUNK, P1, E), set(), {JUNK}))    # t1 + t2
+    tail.append(("v_not_b32 %s, %s" % (E0, E0), set(), set()))                              # ~t2
+    tail.append(("v_subb_co_u32 %s, %s, -1, %s, %s" % (U0, JUNK, V1, cB), {cB}, {JUNK}))    # ~t3
+    tail.append(("v_mad_u64_u32 %s, %s, %s, 1, %s" % (Lin, JUNK, P0, E), set(), {JUNK}))    # t0 + ~t2
+    tail.append(("v_mad_u64_u32 %s, %s, %s, 1, %s" % (Lin, JUNK, U0, Lin), set(), {JUNK}))  # + ~t3
+    return head, tail
+
+
+def emit_mul_lazy(n):
+    """n lazy products: the heads round-robin, then the tails two streams at a time, each of
+    the two on an E pair of its own, so one block zeroes two registers however many products it
+    runs (an E pair per stream cost one move per product)."""
+    n_e = min(n, 2)
+    pro = [("v_mov_b32 v%d, 0" % (8 * n + 2 * j + 1), set(), set()) for j in range(n_e)]
+    parts = [mul_lazy_stream(k, 8 * k, 8 * n + 2 * (k % n_e)) for k in range(n)]
+    body = pro + merge([h for h, _ in parts])
+    for g in range(0, n, n_e):
+        body += merge([t for _, t in parts[g:g + n_e]])
+    body = pad(body)
+    args, outs, ins = [], [], []
+    for k in range(n):
+        args += ["uint32_t a0%d" % k, "uint32_t a1%d" % k, "uint32_t b0%d" % k, "uint32_t b1%d" % k,
+                 "uint64_t& Lin%d" % k, "uint64_t& Hin%d" % k]
+        outs += ['[%s%d] "=&v"(%s%d)' % (nm, k, nm, k) for nm in ("Lin", "Hin")]
+        ins += ['[%s%d] "v"(%s%d)' % (nm, k, nm, k) for nm in ("a0", "a1", "b0", "b1")]
+    clob = ['"v%d"' % i for i in range(8 * n + 2 * n_e)] + ['"s%d"' % i for i in range(SGPR_BASE, SGPR_BASE + 26)]
+    n_v = sum(1 for t in body if t.startswith("v_"))
+    lines = ["// %d independent products handed on as limbs: Lin + Hin 2^32 - %d == a * b mod p, Lin < 3 * 2^32, "
+             "Hin < 2^33 (%d VALU instructions)" % (n, LAZY_OFFSET, n_v),
+             "__device__ __forceinline__ void mul_lazy_x%d(%s) {" % (n, ", ".join(args)), "    asm volatile("]
+    lines += ['        "%s\\n"' % t for t in body]
+    lines += ["        : %s" % ", ".join(outs), "        : %s" % ", ".join(ins), "        : %s);" % ", ".join(clob),
+              "}"]
+    return "\n".join(lines) + "\n"
+
+
 def reduce_stream(k, vbase, pair_out=False):
     """z = L + H * 2^32 mod p for a 64-bit pair L and H = (Hhi:Hlo) given as two 32-bit
     operands, with L < 2^63 and Hhi < 2^31 (so Hhi * EPS + L < 2^64).  These bounds hold
@@ -627,6 +699,9 @@ namespace glasm {
     parts.append(emit_fn("mul_sb_x4", 4, mul_stream, 10, ["a0", "a1", "b0", "b1"], ["z0", "z1"],
                          in_cons={"b0": "s", "b1": "s"},
                          doc="4 independent products z = a * b mod p, b wave-uniform in SGPRs (14 instructions each)"))
+    # the full rounds' last S-box product, handed to the external MDS as limbs (the callers run
+    # four elements at a time, so only the 4-way form exists)
+    parts.append(emit_mul_lazy(4))
     for n in (1, 2, 3, 4):
         parts.append(emit_fn("reduce_x%d" % n, n, lambda k, vb: reduce_stream(k, vb, pair_out=True), 4,
                              ["L", "Hlo", "Hhi"], ["z"], in_kinds={"L": "uint64_t"}, out_kinds={"z": "uint64_t"},

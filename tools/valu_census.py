@@ -99,6 +99,19 @@ def census(instrs, trips=(4, 9, 2)):
     return valu, slots, hist
 
 
+def product_buckets(hist):
+    """The S-box products of one permutation, told apart by what only they issue: a lazy product
+    (glasm::mul_lazy_x4, the full rounds' last product per element, handed to the external MDS
+    as limbs) has the permutation's only v_not_b32 and one v_subb_co_u32, a general product
+    (mul_x*) three v_subb_co_u32.  A lazy product is 12 instructions (11 half-rate, the
+    v_not_b32 full-rate), and each 4-way block zeroes two scratch registers (v_mov_b32)."""
+    lazy = sum(n for mn, n in hist.items() if mn.startswith("v_not_b32"))
+    subb = sum(n for mn, n in hist.items() if mn.startswith("v_subb_co_u32"))
+    general = (subb - lazy) // 3
+    return {"general": {"count": general, "valu": 14 * general, "slots": 28 * general},
+            "lazy": {"count": lazy, "valu": 12 * lazy + lazy // 2, "slots": 23 * lazy + lazy // 2}}
+
+
 def straight_line(instrs):
     """(VALU instructions, issue slots) of a kernel without loops, every instruction once."""
     valu = slots = 0
@@ -206,9 +219,12 @@ def main():
         forms[form] = {"valu": valu, "slots": slots}
         if form == "all":
             top = dict(sorted(hist.items(), key=lambda kv: -kv[1])[:12])
+        if form == "cap":
+            products = product_buckets(hist)
     res = {"kernel": "census_perm_{all,cap,digest} (tools/census_perm.hip: one Poseidon2 permutation per lane)",
            "valu_instr_per_perm": forms["all"]["valu"], "issue_slots_per_perm": forms["all"]["slots"],
            "perm_forms": forms,
+           "products_cap_form": products,
            "top": top,
            "ntt_ct": ntt_census(),
            "lde3": lde3_census(),
