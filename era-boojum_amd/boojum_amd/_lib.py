@@ -116,6 +116,8 @@ SIGNATURES = {
     "bj_gate_set_release": ([_vp], _int),
     "bj_quotient_gate_terms_d": ([_vp, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _u32, _u32, _u32,
                                   _vp, _vp, _vp], _int),
+    "bj_gate_set_satisfied_d": ([_vp, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _u64, _u64, _vp, _vp],
+                                _int),
     "bj_oracle_query_words": ([_qop], _sz),
     "bj_oracle_queries_d": ([_qop, _u32, _vp, _u32, _vp, _sz, _vp, _vp], _int),
     "bj_pow_search_d": ([_u32, ctypes.c_char_p, _sz, _u32, _u64, _u64, _vp, _vp], _int),

@@ -14,7 +14,11 @@ gpu_synthesizer/mod.rs captures from an evaluator's `evaluate_once`:
   reference does for a CSGeometry;
 * `compile_gate_set` (host only): slot allocation by liveness, the split into launches and the
   upload image; `GateSet`: validation (bj_gate_set_check_h) and the one upload;
-* `evaluate_gate_terms`: dst += the gate terms, one launch per segment.
+* `evaluate_gate_terms`: dst += the gate terms, one launch per segment;
+* `check_if_satisfied` -> `SatisfiabilityReport`: the reference's check_if_satisfied
+  (cs/implementations/satisfiability_test.rs:15-353) over the trace columns, on the device
+  (bj_gate_set_satisfied_d): the number of unsatisfied (row, term) pairs and the first one's row,
+  gate, subinstance, term and value; `GateSet.locate_term` maps the running term index back.
 
 The evaluators at the end are written as plain functions over a field-like, so the same function
 runs over `TracingField` to give the program and over any other field-like (the tests' Python
@@ -27,7 +31,7 @@ import numpy as np
 import torch
 
 from ._lib import call, load
-from .field import P, stream_of, to_device
+from .field import P, stream_of, to_device, to_host
 
 MAX_SLOTS = 16              # BJ_GATE_MAX_SLOTS
 MAX_SELECTOR_DEPTH = 8      # BJ_GATE_MAX_SELECTOR_DEPTH
@@ -424,29 +428,83 @@ def check_image(image):
     return dict(variables=need[0], witnesses=need[1], constants=need[2], alphas=need[3], segments=need[4])
 
 
+class TermMap:
+    """The running term index k of a set (the index of the challenges) -> (gate, subinstance, term):
+    host arithmetic over the descriptors of an image.  Gates count on across segments, so `gate` is
+    the index into the placements the image was compiled from; a gate's terms run repetition by
+    repetition, its writes in push order within each."""
+
+    def __init__(self, image):
+        self.gates = []   # (first k, repetitions, terms per repetition), in order
+        k = 0
+        for s in range(image[1]):
+            seg = image[2 + s]
+            if image[seg + 4] != k:
+                raise ValueError("a segment's alpha base is not the sum of the terms before it")
+            for g in range(image[seg]):
+                d = seg + 8 + 8 * g
+                writes = (image[d + 1] >> 32) - (image[d + 1] & 0xffffffff)
+                reps = image[d + 2] & 0xffffffff
+                if writes <= 0 or reps == 0:
+                    raise ValueError("a gate without terms or repetitions")
+                self.gates.append((k, reps, writes))
+                k += reps * writes
+        self.num_terms = k
+
+    def locate(self, k):
+        k = int(k)
+        if not 0 <= k < self.num_terms:
+            raise IndexError("term %d of %d" % (k, self.num_terms))
+        lo, hi = 0, len(self.gates) - 1
+        while lo < hi:   # the last gate whose first k is <= k
+            mid = (lo + hi + 1) // 2
+            if self.gates[mid][0] <= k:
+                lo = mid
+            else:
+                hi = mid - 1
+        first, _, writes = self.gates[lo]
+        return lo, (k - first) // writes, (k - first) % writes
+
+
 class GateSet:
     """Slot allocation, validation and the single upload of a gate set; keeps the device buffer
     alive until it is collected or `release()`d.  `GateSet.from_image` uploads a prepared image."""
 
     def __init__(self, placements, slot_cap=MAX_SLOTS):
         self._handle = None
-        self._upload(compile_gate_set(placements, slot_cap))
+        self.placements = list(placements)
+        self._upload(compile_gate_set(self.placements, slot_cap))
 
     @classmethod
     def from_image(cls, image):
         self = cls.__new__(cls)
         self._handle = None
+        self.placements = None
         self._upload(list(image))
         return self
 
     def _upload(self, image):
         self.image = image
         self.need = check_image(image)
+        self.term_map = TermMap(image)
         handle = ctypes.c_void_p()
         call("bj_gate_set_upload_d", (ctypes.c_uint64 * len(image))(*image), len(image), ctypes.byref(handle))
         self._handle = handle
         self.num_segments = self.need["segments"]
         self.num_terms = self.need["alphas"]
+
+    def locate_term(self, k):
+        """The running term index k -> (gate, subinstance, term): the index into the set's
+        placements, the repetition and the term within it (TermMap)."""
+        return self.term_map.locate(k)
+
+    def gate_name(self, gate):
+        """The name of the evaluator of placement `gate`; None for an uploaded image or a program
+        that was not captured from an evaluator."""
+        if self.placements is None:
+            return None
+        evaluator = self.placements[gate].program.evaluator
+        return evaluator.name if evaluator is not None else None
 
     def release(self):
         if self._handle is not None:
@@ -516,6 +574,96 @@ def evaluate_gate_terms(gate_set, variables_lde, witnesses_lde, constants_lde, a
         call("bj_quotient_gate_terms_d", gate_set._handle, segment, v, v_stride, n_v, w, w_stride, n_w, c, c_stride,
              n_c, alphas.data_ptr(), alphas.shape[0], _log2(n), log_q, dst_c0.data_ptr(), dst_c1.data_ptr(),
              stream_of(dst_c0))
+
+
+# ------------------------------------------------------------------ satisfiability check
+CHECK_BEGIN = 0x80000000    # BJ_GATE_CHECK_BEGIN
+_NO_KEY = (1 << 64) - 1
+
+
+class SatisfiabilityReport:
+    """What check_if_satisfied found.  satisfied; num_unsatisfied, the exact number of (row, term)
+    pairs with selector * term != 0 in the window; and, for the first of them in (row, k) order:
+    row, gate (index into the set's placements), gate_name (the evaluator's name, None for
+    GateSet.from_image), subinstance (the repetition), term (within the repetition), k (the running
+    term index) and value (the term's canonical value).  All None but the first two when
+    satisfied."""
+
+    def __init__(self, num_unsatisfied, row=None, gate=None, gate_name=None, subinstance=None, term=None, k=None,
+                 value=None):
+        self.satisfied = num_unsatisfied == 0
+        self.num_unsatisfied = num_unsatisfied
+        self.row, self.gate, self.gate_name = row, gate, gate_name
+        self.subinstance, self.term, self.k, self.value = subinstance, term, k, value
+
+    def message(self):
+        """The reference's panic (satisfiability_test.rs:149-152), the value in GoldilocksField's
+        Display form; None when satisfied.  A gate without a name is given by its index."""
+        if self.satisfied:
+            return None
+        name = self.gate_name if self.gate_name is not None else "#%d" % self.gate
+        return "Unsatisfied at row %d with value 0x%016x for term number %d for subinstance number %d of gate %s" % (
+            self.row, self.value, self.term, self.subinstance, name)
+
+    def __repr__(self):
+        return "SatisfiabilityReport(satisfied)" if self.satisfied else \
+            "SatisfiabilityReport(%d unsatisfied; %s)" % (self.num_unsatisfied, self.message())
+
+
+def report_from_status(gate_set, status):
+    """The 4 words of the status record of bj_gate_set_satisfied_d -> SatisfiabilityReport.
+    gate_set: anything with locate_term and gate_name."""
+    count, key, value = int(status[0]), int(status[1]), int(status[2])
+    if count == 0:
+        if key != _NO_KEY:
+            raise ValueError("a status record without failures carries a key")
+        return SatisfiabilityReport(0)
+    row, k = key >> 32, key & 0xffffffff
+    gate, subinstance, term = gate_set.locate_term(k)
+    return SatisfiabilityReport(count, row, gate, gate_set.gate_name(gate), subinstance, term, k, value)
+
+
+def _trace(t, what):
+    """(data pointer, column stride, columns, n) of (C, n) trace columns, or zeros for None."""
+    if t is None:
+        return None, 0, 0, None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.int64, torch.uint64):
+        raise TypeError("%s: expected an int64 CUDA tensor of u64 field elements" % what)
+    if t.dim() != 2:
+        raise ValueError("%s: trace columns are (C, n)" % what)
+    c, n = t.shape
+    if n and t.stride(1) != 1:
+        raise ValueError("%s: the rows of a trace column must be contiguous" % what)
+    return t.data_ptr(), (t.stride(0) if c > 1 else n), c, n
+
+
+def check_if_satisfied(gate_set, variables, witnesses, constants, rows=None, status=None):
+    """CSReferenceAssembly::check_if_satisfied (satisfiability_test.rs:15-353) on the device: every
+    gate of gate_set on every row of the window, over the (C, n) trace columns the commitment takes
+    (not an LDE); one the set never names may be None.  rows: a (begin, count) window, default the
+    whole trace.  One bj_gate_set_satisfied_d call per segment on one status record (`status`: a
+    4-word int64 device tensor to use for it), then one copy of its 4 words to the host, which
+    synchronises.  Returns a SatisfiabilityReport."""
+    v, v_stride, n_v, n1 = _trace(variables, "variables")
+    w, w_stride, n_w, n2 = _trace(witnesses, "witnesses")
+    c, c_stride, n_c, n3 = _trace(constants, "constants")
+    sizes = {n for n in (n1, n2, n3) if n is not None}
+    if len(sizes) != 1:
+        raise ValueError("the trace columns disagree on the number of rows" if sizes else "no trace columns")
+    n = sizes.pop()
+    begin, count = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if begin < 0 or count < 1 or begin + count > n:
+        raise ValueError("rows (%d, %d): a window of at least one row inside the %d of the trace" % (begin, count, n))
+    first = next(t for t in (variables, witnesses, constants) if t is not None)
+    if status is None:
+        status = torch.empty((4,), dtype=torch.int64, device=first.device)
+    elif not status.is_cuda or status.dtype not in (torch.int64, torch.uint64) or status.numel() != 4 \
+            or not status.is_contiguous():
+        raise ValueError("status: 4 contiguous int64 words on the device")
+    for segment in range(gate_set.num_segments):
+        call("bj_gate_set_satisfied_d", gate_set._handle, segment | (CHECK_BEGIN if segment == 0 else 0), v, v_stride,
+             n_v, w, w_stride, n_w, c, c_stride, n_c, begin, count, status.data_ptr(), stream_of(first))
+    return report_from_status(gate_set, [int(x) for x in to_host(status)])
 
 
 # ------------------------------------------------------------------ evaluators

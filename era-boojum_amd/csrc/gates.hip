@@ -42,6 +42,10 @@
 //
 // One call launches one segment.  A gate set over the caps is split into segments by the caller,
 // which is exact because the call adds to the accumulator and a segment carries its alpha base.
+//
+// The same image also answers where a witness fails its gates (check_if_satisfied,
+// cs/implementations/satisfiability_test.rs:15-353): gate_check_kernel below walks the programs over
+// trace rows and reports the count and the first failing (row, term) in a status record.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <new>
@@ -165,6 +169,133 @@ __global__ __launch_bounds__(GT_THREADS) void gate_terms_kernel(const uint64_t* 
     if (in) {
         dst0[L] = gl::canon(gl::add(acc0, dst0[L]));
         dst1[L] = gl::canon(gl::add(acc1, dst1[L]));
+    }
+}
+
+// ------------------------------------------------------------------ satisfiability check
+// The same walk over trace columns (no LDE, no challenges, no accumulator): term k of row r fails
+// iff selector_g(r) * term_k(r) != 0, k being the running term index the alphas use (the segment's
+// alpha base carries it on).  One row of the window per lane; a lane past the window walks the
+// window's first row, so its loads stay in bounds, and counts nothing.  A lane keeps its number of
+// failures and the first failing k (k only grows, so the first is the smallest); a wave reduces
+// both with shuffles and, only if it saw a failure, issues one 64-bit add and one 64-bit min on the
+// status record: [0] += count, [1] = min(row << 32 | k).
+//
+// VALUE = true is the second, one-wave launch of the call: every lane walks the row of the record's
+// key and lane 0 writes the canonical value of term k to [2] -- only when k lies in this segment
+// and the row in this window, so the value follows the key across the calls of a set.
+constexpr uint64_t GC_NONE = ~0ULL;
+constexpr uint32_t GC_WAVE = 64;
+
+__global__ void gate_check_begin_kernel(unsigned long long* __restrict__ status) {
+    if (threadIdx.x < 4) status[threadIdx.x] = threadIdx.x == 1 ? GC_NONE : 0;
+}
+
+template <bool VALUE>
+__global__ __launch_bounds__(GT_THREADS) void gate_check_kernel(const uint64_t* __restrict__ seg, Cols cols,
+                                                                uint64_t row_begin, uint64_t n_rows,
+                                                                unsigned long long* __restrict__ status) {
+    __shared__ uint64_t lds[GT_SLOTS * GT_THREADS];
+    uint64_t* slots = lds + threadIdx.x;
+    uint32_t k = (uint32_t)uword(seg + 4);
+    bool in;
+    size_t L;
+    uint32_t target = 0;
+    if constexpr (VALUE) {
+        const uint64_t key = uword(reinterpret_cast<const uint64_t*>(status) + 1);
+        const uint64_t row = key >> 32;
+        target = (uint32_t)key;
+        if (key == GC_NONE || target < k || target - k >= uword(seg + 5)) return;
+        if (row < row_begin || row - row_begin >= n_rows) return;
+        in = true;
+        L = (size_t)row;
+    } else {
+        const size_t l = blockIdx.x * (size_t)GT_THREADS + threadIdx.x;
+        in = l < n_rows;
+        L = (size_t)row_begin + (in ? l : 0);  // a lane past the window reads its first row and counts nothing
+    }
+
+    const uint32_t n_gates = (uint32_t)uword(seg + 0), n_instr = (uint32_t)uword(seg + 1);
+    const uint32_t n_writes = (uint32_t)uword(seg + 2), sel_cols = (uint32_t)uword(seg + 6);
+    const uint64_t* __restrict__ desc = seg + GT_HDR;
+    const uint64_t* __restrict__ instr = desc + (size_t)n_gates * GT_DESC;
+    const uint64_t* __restrict__ writes = instr + n_instr;
+    const uint64_t* __restrict__ imm = writes + n_writes;
+
+    uint64_t selc[GT_SEL];
+    if constexpr (!VALUE) {
+#pragma unroll
+        for (uint32_t i = 0; i < GT_SEL; i++) selc[i] = i < sel_cols ? cols.p[2][(size_t)i * cols.stride[2] + L] : 0;
+    }
+
+    uint64_t count = 0;
+    uint32_t first = 0;
+    for (uint32_t g = 0; g < n_gates; g++) {
+        const uint64_t* __restrict__ d = desc + (size_t)g * GT_DESC;
+        const uint64_t d0 = uword(d), d1 = uword(d + 1), d2 = uword(d + 2), mask = uword(d + 3);
+        const uint64_t dv = uword(d + 4), dw = uword(d + 5), dc = uword(d + 6);
+        const uint32_t i0 = (uint32_t)d0, i1 = (uint32_t)(d0 >> 32), w0 = (uint32_t)d1, w1 = (uint32_t)(d1 >> 32);
+        const uint32_t reps = (uint32_t)d2, depth = (uint32_t)(d2 >> 32);
+        uint32_t off[3] = {(uint32_t)dv, (uint32_t)dw, (uint32_t)dc};
+        uint64_t sel = 1;
+        if constexpr (!VALUE) {
+#pragma unroll
+            for (uint32_t i = 0; i < GT_SEL; i++) {
+                if (i < depth) {
+                    const uint64_t f = (mask >> i) & 1 ? selc[i] : gl::sub(1, selc[i]);
+                    sel = i == 0 ? f : gl::mul(sel, f);
+                }
+            }
+        }
+        for (uint32_t rep = 0; rep < reps; rep++) {
+            for (uint32_t pc = i0; pc < i1; pc++) {
+                const uint64_t w = uword(instr + pc);
+                const uint32_t op = (uint32_t)w & 0xff, slot = (uint32_t)(w >> 8) & 0xff;
+                const uint64_t a = fetch((uint32_t)(w >> 16) & 0xffffff, cols, off, L, slots, imm);
+                uint64_t r;
+                if (op == OP_DOUBLE) {
+                    r = gl::add(a, a);
+                } else if (op == OP_NEGATE) {
+                    r = gl::sub(0, a);
+                } else if (op == OP_SQUARE) {
+                    r = gl::mul(a, a);
+                } else {
+                    const uint64_t b = fetch((uint32_t)(w >> 40) & 0xffffff, cols, off, L, slots, imm);
+                    r = op == OP_MUL ? gl::mul(a, b) : op == OP_ADD ? gl::add(a, b) : gl::sub(a, b);
+                }
+                slots[slot * GT_THREADS] = r;
+            }
+            for (uint32_t t = w0; t < w1; t++, k++) {
+                const uint64_t v = fetch((uint32_t)uword(writes + t) & 0xffffff, cols, off, L, slots, imm);
+                if constexpr (VALUE) {
+                    if (k == target) {  // wave-uniform: every lane walks the same row
+                        if (threadIdx.x == 0) status[2] = gl::canon(v);
+                        return;
+                    }
+                } else {
+                    const bool fail = in && gl::canon(depth ? gl::mul(v, sel) : v) != 0;
+                    first = fail && count == 0 ? k : first;
+                    count += fail;
+                }
+            }
+            off[0] += (uint32_t)(dv >> 32);
+            off[1] += (uint32_t)(dw >> 32);
+            off[2] += (uint32_t)(dc >> 32);
+        }
+    }
+    if constexpr (!VALUE) {
+        unsigned long long key = count ? ((unsigned long long)L << 32) | first : GC_NONE;
+        unsigned long long sum = count;
+#pragma unroll
+        for (uint32_t o = GC_WAVE / 2; o; o >>= 1) {
+            sum += __shfl_down(sum, o, GC_WAVE);
+            const unsigned long long other = __shfl_down(key, o, GC_WAVE);
+            key = other < key ? other : key;
+        }
+        if ((threadIdx.x & (GC_WAVE - 1)) == 0 && sum) {
+            atomicAdd(&status[0], sum);
+            atomicMin(&status[1], key);
+        }
     }
 }
 
@@ -364,6 +495,56 @@ int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* 
                        dst0, dst1);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BJ_OK : bj::hip_error(e, "quotient gate terms");
+}
+
+int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* vars, size_t vars_stride,
+                            uint32_t n_vars, const uint64_t* wits, size_t wits_stride, uint32_t n_wits,
+                            const uint64_t* consts, size_t consts_stride, uint32_t n_consts, uint64_t row_begin,
+                            uint64_t n_rows, uint64_t* status_d, void* stream) {
+    const bj::GateSet* s = static_cast<const bj::GateSet*>(set);
+    if (!s || s->magic != bj::GT_MAGIC) return bj::set_error(BJ_EINVAL, "bj_gate_set_satisfied_d: not a gate set");
+    const bool begin = segment & BJ_GATE_CHECK_BEGIN;
+    segment &= ~BJ_GATE_CHECK_BEGIN;
+    if (segment >= s->n_segments) return bj::set_error(BJ_EINVAL, "bj_gate_set_satisfied_d: no such segment");
+    if (!status_d) return bj::set_error(BJ_EINVAL, "bj_gate_set_satisfied_d: null status");
+    const uint64_t rows_cap = (uint64_t)1 << 32;
+    if (n_rows == 0 || row_begin > rows_cap || n_rows > rows_cap - row_begin)
+        return bj::set_error(BJ_EINVAL, "bj_gate_set_satisfied_d: the row window is empty or ends past 2^32");
+    if (s->need.alphas >= rows_cap)  // the key holds k in 32 bits, all ones being "none"
+        return bj::set_error(BJ_EINVAL, "bj_gate_set_satisfied_d: the set has 2^32 terms or more");
+    const uint64_t end = row_begin + n_rows;
+    const uint64_t* p[3] = {vars, wits, consts};
+    const size_t stride[3] = {vars_stride, wits_stride, consts_stride};
+    const uint32_t have[3] = {n_vars, n_wits, n_consts};
+    static const char* const name[3] = {"variables", "witnesses", "constants"};
+    bj::Cols cols;
+    for (int k = 0; k < 3; k++) {
+        char msg[160];
+        if (s->need.cols[k] > have[k]) {
+            snprintf(msg, sizeof msg, "gate program: an operand reaches %s column %llu of %u", name[k],
+                     (unsigned long long)(s->need.cols[k] - 1), have[k]);
+            return bj::set_error(BJ_EINVAL, msg);
+        }
+        if (s->need.cols[k] && (!p[k] || stride[k] < end)) {
+            snprintf(msg, sizeof msg, "bj_gate_set_satisfied_d: %s are null or their stride is below row_begin + n_rows",
+                     name[k]);
+            return bj::set_error(BJ_EINVAL, msg);
+        }
+        // a kind no operand names is never read; point it at the record so no lane forms a null address
+        cols.p[k] = s->need.cols[k] ? p[k] : status_d;
+        cols.stride[k] = s->need.cols[k] ? stride[k] : 0;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    unsigned long long* status = reinterpret_cast<unsigned long long*>(status_d);
+    const uint64_t* seg = s->image_d + s->seg_offset[segment];
+    if (begin) hipLaunchKernelGGL(bj::gate_check_begin_kernel, dim3(1), dim3(bj::GC_WAVE), 0, st, status);
+    const size_t blocks = (size_t)((n_rows + bj::GT_THREADS - 1) / bj::GT_THREADS);
+    hipLaunchKernelGGL(bj::gate_check_kernel<false>, dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, st, seg, cols,
+                       row_begin, n_rows, status);
+    hipLaunchKernelGGL(bj::gate_check_kernel<true>, dim3(1), dim3(bj::GC_WAVE), 0, st, seg, cols, row_begin, n_rows,
+                       status);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "gate set satisfiability check");
 }
 
 }  // extern "C"

@@ -760,6 +760,40 @@ int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* 
                              uint32_t n_alphas, uint32_t log_n, uint32_t log_q, uint64_t* dst0, uint64_t* dst1,
                              void* stream);
 
+/* Where a witness fails the gates of an uploaded set (CSReferenceAssembly::check_if_satisfied,
+ * cs/implementations/satisfiability_test.rs:15-353, which evaluates every gate's evaluate_once on
+ * every trace row and panics at the first term that is not zero).  Added after 2.6; detect by symbol
+ * (bj_abi_version() is unchanged).  vars, wits, consts: the TRACE columns (Lagrange form on the
+ * domain of n rows, row r of column c at [c * stride + r], the tensors the commitment takes, not an
+ * LDE), read in place over the rows [row_begin, row_begin + n_rows); a kind the set never names may
+ * be NULL with count 0.  Term k of row r is unsatisfied iff selector_g(r) * term_k(r) != 0 in the
+ * field, selector_g being the path product of the call above (an empty path is 1) and k the running
+ * term index the challenges use: across terms, repetitions, gates and segments (a segment's alpha
+ * base carries it on).  With 0 / 1 selector columns that is the reference's rule -- the gate placed
+ * on the row, and every specialized gate on every row; a selector that is neither 0 nor 1 next to
+ * a non-zero term is reported too, as it would leave a remainder in the quotient.  Any u64
+ * representative is accepted, and a value is zero when it is 0 mod p (the word p is zero).
+ *
+ * status_d: DEVICE u64[4].  [0] the number of unsatisfied (row, term) pairs, [1] the smallest key
+ * row << 32 | k among them, or all ones when [0] is 0, [2] the canonical value of that term (the
+ * term's, not selector * term; 0 when [0] is 0), [3] 0.  One call checks one segment and COMBINES
+ * into the record: the count adds, the key takes the minimum, the value follows the key.  The first
+ * call of a check carries BJ_GATE_CHECK_BEGIN in the top bit of `segment`, which initialises the
+ * record on the stream before the segment is checked; the other segments of the set (in any order,
+ * same columns and window) are further calls on the same record without the bit.
+ * Three launches at most (the initialisation, the check at one row per lane, a one-wave launch that
+ * re-evaluates the row of the winning key for its value); asynchronous on `stream`, no copy, no
+ * allocation and no synchronisation, so it captures into a HIP graph.
+ * BJ_EINVAL (status untouched): not a live handle, no such segment, an operand that reaches a
+ * column index >= its count at the largest repetition, a null pointer that is read, null status_d,
+ * n_rows = 0, row_begin + n_rows > 2^32, a stride below row_begin + n_rows, a set of 2^32 terms or
+ * more. */
+#define BJ_GATE_CHECK_BEGIN 0x80000000u
+int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* vars, size_t vars_stride,
+                            uint32_t n_vars, const uint64_t* wits, size_t wits_stride, uint32_t n_wits,
+                            const uint64_t* consts, size_t consts_stride, uint32_t n_consts, uint64_t row_begin,
+                            uint64_t n_rows, uint64_t* status_d, void* stream);
+
 /* ------------------------------------------------------------------ queries */
 /* The query phase (prover.rs:2161-2266): every OracleQuery of a proof -- the leaf's elements
  * (QuerySource::get_elements, fri/mod.rs:683-927) and its Merkle path (get_proof,
