@@ -23,6 +23,10 @@ package is the host-side mirror of the reference's interface for that path:
   gates    Index, Relation, TracingField, capture, GatePlacement, GateSet, evaluate_gate_terms and a
            small library of evaluators                       (gpu_synthesizer/mod.rs, prover.rs:560-1085,
                                                               buffering_source.rs:157-377, cs/gates/*.rs)
+  witness  WitnessVec, DenseVariablesCopyHint, DenseWitnessCopyHint, WitnessSet, CopyHint,
+           witness_set_from_witness_vec, create_permutation_polys, commit_witness_vec
+                                                             (cs/implementations/witness.rs:387-538,
+                                                              hints/mod.rs, setup.rs:401-484)
   queries  QueryOracle, construct_queries, OracleQuery, single_round_queries, fri_plan
                                                              (prover.rs:2161-2266, proof.rs:48-116)
   fri      do_fri, FriOracles, fold_by, final_monomials, fold, interpolate
@@ -33,4 +37,4 @@ package is the host-side mirror of the reference's interface for that path:
 from ._lib import BoojumError, load  # noqa: F401
 from .field import P, GENERATOR  # noqa: F401
 
-__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "quotient", "gates", "queries", "pow", "field", "BoojumError", "load", "P", "GENERATOR"]
+__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "quotient", "gates", "witness", "queries", "pow", "field", "BoojumError", "load", "P", "GENERATOR"]

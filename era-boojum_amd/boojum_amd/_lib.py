@@ -118,6 +118,12 @@ SIGNATURES = {
                                   _vp, _vp, _vp], _int),
     "bj_gate_set_satisfied_d": ([_vp, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _u64, _u64, _vp, _vp],
                                 _int),
+    "bj_copy_hint_upload_d": ([_u64p, _u32, _u64, _sz, ctypes.POINTER(_vp)], _int),
+    "bj_copy_hint_release": ([_vp], _int),
+    "bj_copy_hint_info": ([_vp, ctypes.POINTER(_u32), _u64p, _u64p, _u64p], _int),
+    "bj_materialize_columns_d": ([_vp, _vp, _u64, _vp, _sz, _vp], _int),
+    "bj_materialize_multiplicities_d": ([_vp, _u64, _vp, _u64, _vp], _int),
+    "bj_permutation_polys_d": ([_vp, _u32, _u64, _u64p, _vp, _sz, _vp], _int),
     "bj_oracle_query_words": ([_qop], _sz),
     "bj_oracle_queries_d": ([_qop, _u32, _vp, _u32, _vp, _sz, _vp, _vp], _int),
     "bj_pow_search_d": ([_u32, ctypes.c_char_p, _sz, _u32, _u64, _u64, _vp, _vp], _int),

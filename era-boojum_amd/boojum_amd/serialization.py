@@ -17,6 +17,13 @@ integers little-endian u64:
 * MerkleTreeWithCap (merkle_tree.rs:36-73): cap_size, the leaf hashes as Vec<H::Output>, then
   write_vec_into_buffer of node_hashes_enumerated_from_leafs: the number of levels, then each
   level as Vec<H::Output> (fast_serialization.rs:17-47).
+* WitnessVec (witness.rs:42-70): public_inputs_locations through write_vec_into_buffer (the
+  count, then each (usize, usize) as two u64, fast_serialization.rs:34-47, 83-121), all_values as
+  Vec<F> (as it is: a WitnessVec's words are not canonicalised here), multiplicities as the count
+  and then the u32 counts, 4 bytes each (fast_serialization.rs:49-64; Vec<u32> at :210-237 has the
+  same bytes).
+* DenseVariablesCopyHint / DenseWitnessCopyHint (hints/mod.rs:22-136): the number of columns, then
+  each column as its length and its Variable / Witness words, 8 bytes each.
 Every value this library writes is canonical. The reference writes its in-memory words, which
 may be non-canonical representatives of the same elements; readers compare canonically
 (goldilocks/mod.rs:257-261).
@@ -132,6 +139,53 @@ def read_merkle_tree(f, hasher="poseidon2"):
     n = _read_u64(f)
     levels = [read_digests(f, hasher) for _ in range(n)]
     return cap_size, leaves, levels
+
+
+# ------------------------------------------------------------- WitnessVec and the dense hints
+def write_witness_vec(f, witness_vec):
+    """MemcopySerializable for WitnessVec (witness.rs:60-69)."""
+    _write_u64(f, len(witness_vec.public_inputs_locations))
+    for column, row in witness_vec.public_inputs_locations:
+        _write_u64(f, column)
+        _write_u64(f, row)
+    _write_words(f, np.asarray(_host(witness_vec.all_values)).reshape(-1))
+    m = witness_vec.multiplicities
+    m = m.detach().cpu().numpy().view(np.uint32) if isinstance(m, torch.Tensor) else np.asarray(m, dtype=np.uint32)
+    _write_u64(f, m.size)
+    f.write(np.ascontiguousarray(m).astype("<u4", copy=False).tobytes())
+
+
+def read_witness_vec(f):
+    """-> boojum_amd.witness.WitnessVec with numpy all_values (uint64) and multiplicities (uint32)
+    (witness.rs:46-58)."""
+    from .witness import WitnessVec
+    locations = [(_read_u64(f), _read_u64(f)) for _ in range(_read_u64(f))]
+    all_values = _read_words(f)
+    n = _read_u64(f)
+    b = f.read(4 * n)
+    if len(b) != 4 * n:
+        raise EOFError("truncated MemcopySerializable stream")
+    return WitnessVec(locations, all_values, np.frombuffer(b, dtype="<u4").astype(np.uint32))
+
+
+def write_copy_hint(f, hint):
+    """MemcopySerializable for DenseVariablesCopyHint / DenseWitnessCopyHint (hints/mod.rs:104-136):
+    hint is one of them, a boojum_amd.witness.CopyHint, or the maps."""
+    from .witness import hint_words
+    words = getattr(hint, "words", None)
+    if words is None:
+        words = hint_words(hint)
+    _write_u64(f, words.shape[0])
+    for column in words:
+        _write_words(f, column)
+
+
+def read_copy_hint(f, kind=None):
+    """-> kind(maps) with maps a list of uint64 columns; kind: DenseVariablesCopyHint (the default)
+    or DenseWitnessCopyHint, whose bytes are the same (hints/mod.rs:22-102)."""
+    from .witness import DenseVariablesCopyHint
+    maps = [_read_words(f) for _ in range(_read_u64(f))]
+    return (kind or DenseVariablesCopyHint)(maps)
 
 
 # ------------------------------------------------------------- serde JSON (proof format)

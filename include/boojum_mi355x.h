@@ -794,6 +794,71 @@ int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* v
                             const uint64_t* consts, size_t consts_stride, uint32_t n_consts, uint64_t row_begin,
                             uint64_t n_rows, uint64_t* status_d, void* stream);
 
+/* ------------------------------------------------------------------ witness materialisation */
+/* The trace columns from a WitnessVec and the circuit's dense copy hints
+ * (CSReferenceAssembly::witness_set_from_witness_vec, cs/implementations/witness.rs:387-538; the
+ * same loops in materialize_witness_polynomials, :108-385; the hints, cs/implementations/hints/mod.rs),
+ * the first step of prove_from_precomputations, and the sigma columns of the setup from the same
+ * placement (create_permutation_polys, setup.rs:401-484).  Added after 2.6; detect by symbol
+ * (bj_abi_version() is unchanged).  The hints are fixed per circuit and stay on the device; a proof
+ * uploads all_values, one word per distinct variable, and the columns appear where the commitment,
+ * stage 2 and the satisfiability check read them.
+ *
+ * A hint is uploaded once.  words: HOST memory, the reference's own words, column-major: cell
+ * (c, r) at words[c * stride + r], n_cols columns of n_rows rows.  A Variable or Witness is a u64
+ * (cs/mod.rs:159-213): bit 63 marks a placeholder, the low 48 bits hold the index, the other bits
+ * are ignored as as_variable_index / as_witness_index ignore them (cs/mod.rs:44-47).  The device
+ * copy holds one u32 per cell, 2^32 - 1 standing for the placeholder, which halves the index
+ * traffic of every proof; so an index must be below 2^32 - 1, and a word that names a larger one
+ * is BJ_EINVAL (the reference's as_variable_index truncates it to 32 bits silently).  The upload
+ * packs on the host, records the largest index and the number of placeholders, allocates
+ * 4 * n_cols * n_rows bytes on the current device, copies and synchronises.  *hint keeps the device
+ * buffer until bj_copy_hint_release (NULL is a no-op); on failure *hint is NULL.
+ * BJ_EINVAL: null words or hint, n_cols = 0, n_rows = 0 or above 2^32, stride < n_rows, an index
+ * of 2^32 - 1 or more. */
+int bj_copy_hint_upload_d(const uint64_t* words, uint32_t n_cols, uint64_t n_rows, size_t stride, void** hint);
+int bj_copy_hint_release(void* hint);
+/* What the upload recorded; any out pointer may be NULL.  max_index is 0 for a hint of nothing but
+ * placeholders.  Host only.  BJ_EINVAL: not a live handle. */
+int bj_copy_hint_info(const void* hint, uint32_t* n_cols, uint64_t* n_rows, uint64_t* max_index,
+                      uint64_t* n_placeholders);
+
+/* The copy loops of witness_set_from_witness_vec (witness.rs:419-441 for the variables, :466-488 for
+ * the witnesses): out[c * out_stride + r] = all_values[index of cell (c, r)], or 0 for a placeholder
+ * (:434-436).  all_values: DEVICE array of num_values words, moved bit for bit: a non-canonical word
+ * stays as it is, as the LDE accepts such columns.  Words of out between n_rows and out_stride are
+ * not written.  The call compares num_values with the hint's largest index on the host, so no lane
+ * checks a bound and no kernel can read outside all_values; nothing is copied back.  One launch, no
+ * allocation and no synchronisation, the hint travelling by value: it captures into a HIP graph on
+ * `stream`, and a replay reads the contents all_values has then.
+ * BJ_EINVAL (nothing launched, out untouched): not a live handle, a null pointer,
+ * num_values <= max_index, out_stride < n_rows. */
+int bj_materialize_columns_d(const void* hint, const uint64_t* all_values, uint64_t num_values, uint64_t* out,
+                             size_t out_stride, void* stream);
+
+/* The multiplicity column (witness.rs:493-519): out[i] = mult_u32[i] widened (from_u64_unchecked of
+ * the u32, :515) for i < len, 0 for len <= i < n_rows.  mult_u32: DEVICE array, may be NULL when
+ * len is 0.  One launch.  BJ_EINVAL: len > n_rows, n_rows = 0, a null pointer that is read. */
+int bj_materialize_multiplicities_d(const uint32_t* mult_u32, uint64_t len, uint64_t* out, uint64_t n_rows,
+                                    void* stream);
+
+/* create_permutation_polys (setup.rs:401-484) as one elementwise pass.  The identity value of cell
+ * (col, row) is non_residues[col] * w_n^row, rows in natural order (materialize_x_by_non_residue_polys,
+ * setup.rs:24-76, over materialize_x_poly, utils.rs:690-721).  prev: DEVICE map of n_cols * n_rows
+ * u32, cell (c, r) at prev[c * n_rows + r]: the flat index col * n_rows + row of the cell whose
+ * identity value the cell takes -- the variable's previous occurrence in (column, row) order, the
+ * last occurrence for the first one, and the cell itself for a placeholder or a variable's only
+ * occurrence.  That is what the reference's chain of swaps (:428-471) leaves behind.  out[c *
+ * out_stride + r] receives the value, canonical: one product of two table entries per cell.  An
+ * entry of prev that names no cell gives 0, which is no identity value, and reads nothing.
+ * non_residues: HOST array of n_cols words (bj_non_residues_h).  A setup-time call: it takes
+ * 8 * (n_cols + n_rows / 2) bytes from the library's pool for its table, filled by the kernel of
+ * bj_precompute_twiddles_natural_d, and synchronises `stream` once for the copy of non_residues.
+ * BJ_EINVAL: n_rows no power of two or above 2^32, n_cols outside 1..65535, n_cols * n_rows >
+ * 2^32, out_stride < n_rows, a null pointer. */
+int bj_permutation_polys_d(const uint32_t* prev, uint32_t n_cols, uint64_t n_rows, const uint64_t* non_residues,
+                           uint64_t* out, size_t out_stride, void* stream);
+
 /* ------------------------------------------------------------------ queries */
 /* The query phase (prover.rs:2161-2266): every OracleQuery of a proof -- the leaf's elements
  * (QuerySource::get_elements, fri/mod.rs:683-927) and its Merkle path (get_proof,
