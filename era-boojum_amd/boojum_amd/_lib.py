@@ -32,6 +32,16 @@ assert ctypes.sizeof(QueryOracleDesc) == 56
 QUERY_MAX_ORACLES = 16  # BJ_QUERY_MAX_ORACLES
 _qop = ctypes.POINTER(QueryOracleDesc)
 
+
+class ShardedQueryOracleDesc(ctypes.Structure):
+    """bj_sharded_query_oracle_t (include/boojum_mi355x.h), 56 bytes."""
+    _fields_ = [("src", _vp), ("col_stride", _sz), ("n_cols", _u32), ("hasher", ctypes.c_int32),
+                ("leaves", _vp), ("nodes", _vp), ("n_leaves", _u64), ("cap_size", _u32), ("reserved", _u32)]
+
+
+assert ctypes.sizeof(ShardedQueryOracleDesc) == 56
+_sqop = ctypes.POINTER(ShardedQueryOracleDesc)
+
 # name -> argtypes (restype int unless noted).  Every symbol the header declares.
 SIGNATURES = {
     "bj_last_error": ([], ctypes.c_char_p),
@@ -126,6 +136,8 @@ SIGNATURES = {
     "bj_permutation_polys_d": ([_vp, _u32, _u64, _u64p, _vp, _sz, _vp], _int),
     "bj_oracle_query_words": ([_qop], _sz),
     "bj_oracle_queries_d": ([_qop, _u32, _vp, _u32, _vp, _sz, _vp, _vp], _int),
+    "bj_sharded_query_words": ([_sqop], _sz),
+    "bj_sharded_queries_d": ([_vp, _sqop, _u32, _vp, _u32, _vp, _sz, _vp, _vp], _int),
     "bj_pow_search_d": ([_u32, ctypes.c_char_p, _sz, _u32, _u64, _u64, _vp, _vp], _int),
     "bj_pow_run_h": ([_u32, ctypes.c_char_p, _sz, _u32, _u64p], _int),
     "bj_pow_verify_h": ([_u32, ctypes.c_char_p, _sz, _u32, _u64], _int),

@@ -18,8 +18,10 @@ per rank, `bj_sharded_commit_d` (csrc/collective.hip):
 
 This module is the host side of that call: communicators (`NativeComm`: RCCL, an in-process
 group of ranks on one device, or a torch.distributed group through the callback transport),
-the output buffers, and the query.  There is one pipeline: the bench, the tests and the
-multi-GPU runs all go through `bj_sharded_commit_d`.
+the output buffers, and the queries: one index of one oracle per call (`native_sharded_query`,
+bj_sharded_query_h) or every index of up to 16 sharded oracles in one collective call
+(`native_sharded_queries`, bj_sharded_queries_d).  There is one pipeline:
+the bench, the tests and the multi-GPU runs all go through `bj_sharded_commit_d`.
 """
 import ctypes
 
@@ -280,3 +282,88 @@ def native_sharded_query(comm, res, n_cols, log_n, log_lde, cap_size, tree_idx, 
          log_n, log_lde, log_k, cap_size, HASHER_IDS[hasher], tree_idx, p(elems), p(leaf), p(proof),
          stream_of(res.lde))
     return elems, leaf, proof[:depth]
+
+
+class ShardedQueryOracle:
+    """One oracle of bj_sharded_queries_d: this rank's NativeShardedResult `res` of a commit of n_cols
+    columns of 2^log_n at D = 2^log_lde, tree over the first 2^log_commit_cosets cosets (all D by
+    default) with the global `cap_size`.  The leaf sources are block 0 of res.lde, column stride m;
+    sources=False answers paths only."""
+
+    def __init__(self, res, n_cols, log_n, log_lde, cap_size, hasher="poseidon2", log_commit_cosets=None,
+                 sources=True):
+        log_k = log_lde if log_commit_cosets is None else log_commit_cosets
+        self.res, self.hasher = res, hasher
+        self.n_leaves, self.cap_size = 1 << (log_n + log_k), cap_size
+        self.depth = (log_n + log_k) - _log2(cap_size)
+        self.n_cols = self.n_elements = n_cols if sources else 0
+        self.col_stride = res.lde.stride(1) if sources else 0
+        self.words = self.n_cols + 4 + 4 * self.depth
+
+    def descriptor(self):
+        from ._lib import ShardedQueryOracleDesc
+        r = self.res
+        return ShardedQueryOracleDesc(r.lde[0].data_ptr() if self.n_cols else None, self.col_stride, self.n_cols,
+                                      HASHER_IDS[self.hasher], r.leaves.data_ptr(), r.nodes.data_ptr(),
+                                      self.n_leaves, self.cap_size, 0)
+
+
+def sharded_query_words(oracle):
+    """bj_sharded_query_words of a ShardedQueryOracle, asked of the library."""
+    return int(load().bj_sharded_query_words(ctypes.byref(oracle.descriptor())))
+
+
+def launch_sharded_queries(comm, oracles, indices_d, out_d, status_d):
+    """The bare bj_sharded_queries_d call on the current stream of out_d's device (collective,
+    asynchronous).  indices_d: (Q,) int64 device tensor; out_d: at least Q * the sum of the oracles'
+    words; status_d: (4,)."""
+    from ._lib import QUERY_MAX_ORACLES, ShardedQueryOracleDesc
+    if not 1 <= len(oracles) <= QUERY_MAX_ORACLES:
+        raise ValueError("1..%d oracles, got %d" % (QUERY_MAX_ORACLES, len(oracles)))
+    descs = (ShardedQueryOracleDesc * len(oracles))(*[o.descriptor() for o in oracles])
+    call("bj_sharded_queries_d", comm.handle, descs, len(oracles), indices_d.data_ptr(), indices_d.numel(),
+         out_d.data_ptr(), out_d.numel(), status_d.data_ptr(), stream_of(out_d))
+
+
+def native_sharded_queries(comm, oracles, indices):
+    """queries.construct_queries on sharded commits: every oracle's query at every tree index from
+    one bj_sharded_queries_d call on the current stream and one device-to-host copy.  Collective
+    over `comm`: every rank passes its own ShardedQueryOracle list and the same indices (a sequence
+    of ints or an int64 device tensor) and gets the same per-oracle OracleQueries(leaf_elements
+    (Q, C), leaf_hash (Q, 4), proof (Q, depth, 4)) as numpy uint64.  Raises BoojumError when an
+    index is outside the tree."""
+    import numpy as np
+    from ._lib import BoojumError
+    from .field import to_host
+    from .queries import STATUS_WORDS, parse_queries
+    dev = oracles[0].res.leaves.device
+    if isinstance(indices, torch.Tensor):
+        idx = indices.reshape(-1).to(device=dev, dtype=torch.int64)
+    else:
+        idx = torch.from_numpy(np.ascontiguousarray(np.asarray(indices, dtype=np.uint64)).view(np.int64)).to(dev)
+    q = idx.numel()
+    total = q * sum(o.words for o in oracles)
+    # the status record rides behind the records, so one copy brings both
+    buf = torch.empty((total + STATUS_WORDS,), dtype=torch.int64, device=dev)
+    launch_sharded_queries(comm, oracles, idx, buf[:total], buf[total:])
+    host = to_host(buf)
+    status = host[total:]
+    if status[0]:
+        raise BoojumError("%d query index(es) outside the tree of %d leaves, the first at position %d"
+                          % (int(status[0]), oracles[0].n_leaves, int(status[1])))
+    return parse_queries(host[:total], [(o.n_elements, o.depth) for o in oracles], q)
+
+
+def native_sharded_single_round_queries(comm, witness, stage_2, quotient, setup, indices):
+    """queries.single_round_queries for base oracles that stayed sharded (ShardedQueryOracle each):
+    the same serde shape with "fri_queries": [] -- the FRI oracles are not sharded."""
+    from . import serialization
+    oracles = [witness, stage_2, quotient, setup]
+    res = native_sharded_queries(comm, oracles, indices)
+
+    def one(o, q):
+        return serialization.oracle_query_to_json(res[o].leaf_elements[q], res[o].proof[q], oracles[o].hasher)
+
+    return [{"witness_query": one(0, q), "stage_2_query": one(1, q), "quotient_query": one(2, q),
+             "setup_query": one(3, q), "fri_queries": []}
+            for q in range(res[0].leaf_hash.shape[0])]

@@ -31,6 +31,7 @@
 #include "../../include/boojum_mi355x.h"
 #include "bj_internal.hpp"
 #include "gl.hpp"
+#include "queries_sharded.hpp"
 
 namespace {
 
@@ -1002,6 +1003,111 @@ int bj_sharded_query_h(bj_comm* comm, const uint64_t* lde, const uint64_t* leave
                              st),
               "memcpy");
     HIP_CHECK(hipStreamSynchronize(st), "sync");
+    abort_guard.ok = true;
+    return BJ_OK;
+}
+
+size_t bj_sharded_query_words(const bj_sharded_query_oracle_t* o) {
+    if (!o || !is_pow2(o->n_leaves) || !is_pow2(o->cap_size) || o->n_leaves < o->cap_size) return 0;
+    return (size_t)o->n_cols + 4 + 4 * (size_t)(log2u(o->n_leaves) - log2u(o->cap_size));
+}
+
+int bj_sharded_queries_d(bj_comm* comm, const bj_sharded_query_oracle_t* oracles, uint32_t n_oracles,
+                         const uint64_t* indices_d, uint32_t n_queries, uint64_t* out_d, size_t out_words,
+                         uint64_t* status_d, void* stream) {
+    if (!comm) return err(BJ_EINVAL, "null communicator");
+    GroupAbort abort_guard(comm);
+    // every argument check comes before the first exchange: ranks given the same bad arguments
+    // all return instead of waiting on each other
+    if (!oracles || !indices_d || !out_d || !status_d) return err(BJ_EINVAL, "bj_sharded_queries_d: null pointer");
+    if (n_oracles < 1 || n_oracles > BJ_QUERY_MAX_ORACLES)
+        return err(BJ_EINVAL, "bj_sharded_queries_d: n_oracles outside 1..16");
+    if (n_queries == 0) return err(BJ_EINVAL, "bj_sharded_queries_d: n_queries is 0");
+    const uint32_t world = (uint32_t)comm->world, rank = (uint32_t)comm->rank;
+    if (!is_pow2(world)) return err(BJ_EINVAL, "bj_sharded_queries_d: the world size is no power of two");
+    const uint32_t log_g = log2u(world);
+    const uint64_t nl = oracles[0].n_leaves;
+    bj::ShardedQueryArgs a;
+    memset(&a, 0, sizeof a);
+    uint64_t words = 0;
+    uint32_t n_top = 0;  // oracles with cap_size < G
+    for (uint32_t i = 0; i < n_oracles; i++) {
+        const bj_sharded_query_oracle_t& o = oracles[i];
+        const std::string which = "bj_sharded_queries_d: oracle " + std::to_string(i) + ": ";
+        if (!o.leaves || !o.nodes || (o.n_cols && !o.src)) return err(BJ_EINVAL, which + "null pointer");
+        if (!is_pow2(o.n_leaves) || !is_pow2(o.cap_size))
+            return err(BJ_EINVAL, which + "n_leaves and cap_size must be powers of two");
+        if (o.n_leaves != nl) return err(BJ_EINVAL, which + "n_leaves differs from oracle 0's");
+        if (world > nl) return err(BJ_EINVAL, which + "more ranks than leaves");
+        const uint64_t m = nl >> log_g, cap_local = std::max<uint64_t>(1, o.cap_size / world);
+        if (m <= cap_local) return err(BJ_EINVAL, which + "each shard needs more leaves than its cap slice");
+        if (o.n_cols && o.col_stride < m) return err(BJ_EINVAL, which + "col_stride < m");
+        if (!bj::tree_ops(o.hasher)) return err(BJ_EINVAL, which + "unknown hasher");
+        bj::ShardedQueryOracle& d = a.o[i];
+        d.src = o.src;
+        d.col_stride = o.col_stride;
+        d.leaves = o.leaves;
+        d.nodes = o.nodes;
+        d.n_cols = o.n_cols;
+        d.local_depth = log2u(m) - log2u(cap_local);
+        d.top_depth = o.cap_size < world ? log_g - log2u(o.cap_size) : 0;
+        if (d.top_depth) n_top++;
+        words += bj::sharded_query_words(d);
+    }
+    if (words > ~(uint64_t)0 / 8 / world / n_queries || out_words < words * n_queries)
+        return err(BJ_EINVAL, "bj_sharded_queries_d: out_words below n_queries * the oracles' record words");
+    a.n_leaves = nl;
+    a.log_world = log_g;
+    a.rank = rank;
+    const size_t m = (size_t)(nl >> log_g), per_rank = (size_t)(words * n_queries);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    Workspace ws(st);
+
+    // 1. cap < G: the subtree roots of those oracles in one all-gather, then the levels over each
+    //    oracle's G roots, hashed on every rank
+    if (n_top) {
+        uint64_t *mine = nullptr, *all = nullptr, *roots = nullptr, *top = nullptr;
+        HIP_CHECK(ws.alloc(&roots, (size_t)n_top * world * 4), "pool_alloc");
+        HIP_CHECK(ws.alloc(&top, (size_t)n_top * world * 4), "pool_alloc");
+        if (n_top > 1) {
+            HIP_CHECK(ws.alloc(&mine, (size_t)n_top * 4), "pool_alloc");
+            HIP_CHECK(ws.alloc(&all, (size_t)n_top * world * 4), "pool_alloc");
+        }
+        uint32_t t = 0;
+        for (uint32_t i = 0; i < n_oracles; i++) {
+            if (!a.o[i].top_depth) continue;
+            const uint64_t* root = oracles[i].nodes + (m - 2) * 4;  // cap_local = 1: the pair under the root
+            a.o[i].roots = roots + (size_t)t * world * 4;
+            a.o[i].top = top + (size_t)t * world * 4;
+            if (n_top == 1)
+                BJ_CHECK(all_gather(comm, root, roots, 32, st));
+            else
+                HIP_CHECK(hipMemcpyAsync(mine + 4 * t, root, 32, hipMemcpyDeviceToDevice, st), "memcpy root");
+            t++;
+        }
+        if (n_top > 1) BJ_CHECK(all_gather(comm, mine, all, (size_t)n_top * 32, st));
+        t = 0;
+        for (uint32_t i = 0; i < n_oracles; i++) {
+            if (!a.o[i].top_depth) continue;
+            uint64_t* r = roots + (size_t)t * world * 4;
+            // rank p's root of this oracle is digest p * n_top + t of the gathered block
+            if (n_top > 1)
+                HIP_CHECK(hipMemcpy2DAsync(r, 32, all + 4 * t, (size_t)n_top * 32, 32, world, hipMemcpyDeviceToDevice,
+                                           st),
+                          "memcpy roots");
+            BJ_CHECK(bj::tree_nodes(oracles[i].hasher, r, world, oracles[i].cap_size, top + (size_t)t * world * 4, st));
+            t++;
+        }
+    }
+    // 2. the records this rank owns, written in place into its block of the gathered buffer
+    uint64_t* gathered = nullptr;
+    HIP_CHECK(ws.alloc(&gathered, per_rank * world), "pool_alloc");
+    HIP_CHECK(bj::sharded_query_records(a, n_oracles, indices_d, n_queries, gathered + (size_t)rank * per_rank, status_d,
+                                        st),
+              "sharded query records");
+    // 3. every rank's records everywhere, 4. each query's owner's copy
+    BJ_CHECK(all_gather(comm, gathered + (size_t)rank * per_rank, gathered, per_rank * 8, st));
+    HIP_CHECK(bj::sharded_query_select(a, n_oracles, indices_d, n_queries, gathered, out_d, st), "sharded query select");
     abort_guard.ok = true;
     return BJ_OK;
 }

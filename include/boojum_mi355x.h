@@ -913,6 +913,57 @@ size_t bj_oracle_query_words(const bj_query_oracle_t* o);
 int bj_oracle_queries_d(const bj_query_oracle_t* oracles, uint32_t n_oracles, const uint64_t* indices_d,
                         uint32_t n_queries, uint64_t* out_d, size_t out_words, uint64_t* status_d, void* stream);
 
+/* The same batch on trees that bj_sharded_commit_d left sharded: every oracle and every index in
+ * one collective call.  Added after 2.6; detect by symbol (bj_abi_version() is unchanged).  With G
+ * the communicator's world, m = n_leaves / G and cap_local = max(1, cap_size / G), one oracle is
+ * this rank's commit outputs and the GLOBAL tree's geometry. */
+typedef struct bj_sharded_query_oracle {
+    const uint64_t* src;     /* this rank's block 0 of bj_sharded_commit_d's lde: column c at src + c * col_stride,
+                                m rows; NULL iff n_cols == 0 */
+    size_t col_stride;       /* >= m */
+    uint32_t n_cols;         /* 0: path only */
+    int32_t hasher;          /* BJ_HASHER_*: only used to hash the top levels when cap_size < G */
+    const uint64_t* leaves;  /* m x 4, this rank's */
+    const uint64_t* nodes;   /* (m - cap_local) x 4, this rank's subtree */
+    uint64_t n_leaves;       /* of the GLOBAL tree: k * n */
+    uint32_t cap_size;       /* of the GLOBAL tree */
+    uint32_t reserved;
+} bj_sharded_query_oracle_t;
+
+/* Words of one query's record of oracle o: n_cols + 4 + 4 * log2(n_leaves / cap_size), which is
+ * bj_oracle_query_words of the unsharded tree with e = 0.  0 for a null o or sizes that are no
+ * powers of two.  Host only. */
+size_t bj_sharded_query_words(const bj_sharded_query_oracle_t* o);
+
+/* Collective: every rank passes its own shard buffers, the same geometry and the same contents of
+ * indices_d (n_queries device u64, tree indices < n_leaves), and every rank receives the same
+ * out_d and status_d: word for word what bj_oracle_queries_d writes for the unsharded tree with
+ * log_elems_per_leaf = 0 and index_shift = 0.  Oracle o's block starts at out_d + n_queries *
+ * sum_{o' < o} W_o', W = bj_sharded_query_words, and query q's record at + q * W_o: the n_cols
+ * elements of the row, the leaf hash, then the depth siblings in get_proof order -- the first
+ * log2(m / cap_local) from the subtree of the rank that owns the leaf (rank index / m), and when
+ * cap_size < G the remaining log2(G / cap_size) from the levels hashed over the gathered subtree
+ * roots.  Every oracle of a call has the same n_leaves, so a query has one owner for all of them;
+ * cap_size, n_cols and hasher may differ.  status_d[4]: [0] the number of indices >= n_leaves, [1]
+ * the position of the first such index or ~0, [2] = [3] = 0; such a query's records are all zero
+ * on every rank.
+ * Schedule: when an oracle has cap_size < G, one all-gather of those oracles' subtree roots (32
+ * bytes per oracle and rank) and the top levels hashed on every rank; one launch in which the
+ * owner writes its records; one all-gather of every rank's record buffer (G * n_queries * sum_o
+ * W_o * 8 bytes arrive per rank: all ranks' buffers travel, whoever owns the records); one launch
+ * that picks each query's owner's copy.  Two launches and at most two exchanges whatever n_queries
+ * and n_oracles.  Asynchronous on `stream` (the call itself never synchronises; a host-staged
+ * callback transport does inside its exchange); workspace comes from the library's stream-ordered
+ * pool.
+ * BJ_EINVAL, all checked before the first exchange so that ranks given the same bad arguments all
+ * return: a null pointer other than src with n_cols == 0, n_oracles outside 1..16, n_queries = 0,
+ * n_leaves or cap_size no power of two, n_leaves that differ between oracles, G > n_leaves,
+ * m <= cap_local, col_stride < m with n_cols > 0, an unknown hasher, out_words below n_queries *
+ * sum_o W_o. */
+int bj_sharded_queries_d(bj_comm* comm, const bj_sharded_query_oracle_t* oracles, uint32_t n_oracles,
+                         const uint64_t* indices_d, uint32_t n_queries, uint64_t* out_d, size_t out_words,
+                         uint64_t* status_d, void* stream);
+
 /* ------------------------------------------------------------------ proof of work */
 /* PoWRunner (cs/implementations/pow.rs:7-32) for Blake2s256 (pow.rs:51-135) and Keccak256
  * (pow.rs:137-221), the step between the last FRI oracle and the queries (prover.rs:2107-2133).
