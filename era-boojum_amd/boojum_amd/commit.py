@@ -9,13 +9,7 @@ prover running many circuits) never allocate.
 import torch
 
 from ._lib import call
-from .field import col_view, stream_of
-
-
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
+from .field import col_view, log2_exact, stream_of
 
 
 class CommitWorkspace:
@@ -30,7 +24,7 @@ class CommitWorkspace:
             raise ValueError("committed cosets must not exceed the LDE degree")
         n, d = 1 << log_n, 1 << log_lde
         nl = n << log_k
-        _log2(cap_size)
+        log2_exact(cap_size)
         if nl <= cap_size:
             raise ValueError("tree size must exceed cap size")
         self.n_cols, self.log_n, self.log_lde, self.cap_size = n_cols, log_n, log_lde, cap_size
@@ -57,8 +51,8 @@ def witness_commit(trace, lde_degree, cap_size, workspace=None, hasher="poseidon
     hasher: "poseidon2" (GoldilocksPoseidon2Sponge, the recursive-mode tree), "blake2s"
     (Blake2s256, the non-recursive one) or "keccak256"."""
     v, c, n, stride = col_view(trace)
-    log_n, log_d = _log2(n), _log2(lde_degree)
-    log_k = log_d if fri_lde_factor is None else _log2(fri_lde_factor)
+    log_n, log_d = log2_exact(n), log2_exact(lde_degree)
+    log_k = log_d if fri_lde_factor is None else log2_exact(fri_lde_factor)
     ws = workspace or CommitWorkspace(c, log_n, log_d, cap_size, device=v.device, log_commit_cosets=log_k)
     if (ws.n_cols, ws.log_n, ws.log_lde, ws.log_k, ws.cap_size) != (c, log_n, log_d, log_k, cap_size):
         raise ValueError("workspace shape does not match the trace")

@@ -23,25 +23,7 @@ import numpy as np
 import torch
 
 from ._lib import call
-from .field import P, col_view, stream_of, to_device, to_host
-
-EXT2_NON_RESIDUE = 7   # GoldilocksExt2::NON_RESIDUE (field/goldilocks/extension.rs:14-16)
-
-
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
-
-
-def ext2_mul(a, b):
-    """(a0 + a1 u)(b0 + b1 u) with u^2 = 7 (field/traits/field.rs:407-424), on host ints."""
-    return ((a[0] * b[0] + EXT2_NON_RESIDUE * a[1] * b[1]) % P, (a[0] * b[1] + a[1] * b[0]) % P)
-
-
-def ext2_mul_by_u(a):
-    """a * u: (a0 + a1 u) u = 7 a1 + a0 u."""
-    return (EXT2_NON_RESIDUE * a[1] % P, a[0] % P)
+from .field import EXT2_NON_RESIDUE, P, col_view, ext2_mul, ext2_mul_by_u, log2_exact, stream_of, to_device, to_host
 
 
 def materialize_ext_challenge_powers(c, n):
@@ -56,7 +38,7 @@ def materialize_ext_challenge_powers(c, n):
 def precompute_for_barycentric_evaluation_in_extension(n, coset, at, device="cuda"):
     """utils.rs:907-1021: the weights (w0, w1), two (n,) device columns in bit-reversed order, of
     the domain coset * <w_n> at the Ext2 point `at`."""
-    log_n = _log2(n)
+    log_n = log2_exact(n)
     w0 = torch.empty((n,), dtype=torch.int64, device=device)
     w1 = torch.empty_like(w0)
     call("bj_barycentric_weights_d", log_n, coset % P, at[0] % P, at[1] % P, w0.data_ptr(), w1.data_ptr(),
@@ -73,7 +55,7 @@ def barycentric_evaluate_base_at_extension_for_bitreversed(cols_view, w):
     if w0.shape[-1] != n or w1.shape[-1] != n:
         raise ValueError("weights and columns sizes do not match")
     out = torch.empty((c, 2), dtype=torch.int64, device=t.device)
-    call("bj_evaluate_at_d", t.data_ptr(), c, stride, _log2(n), w0.data_ptr(), w1.data_ptr(), out.data_ptr(),
+    call("bj_evaluate_at_d", t.data_ptr(), c, stride, log2_exact(n), w0.data_ptr(), w1.data_ptr(), out.data_ptr(),
          stream_of(t))
     return [(int(a), int(b)) for a, b in to_host(out)]
 

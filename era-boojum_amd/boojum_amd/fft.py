@@ -12,20 +12,10 @@ PrimeFieldLikeVectorized seam (field/traits/field_like.rs:111-162):
 Errors: preconditions the reference asserts (power-of-two sizes, fft/mod.rs:399-402)
 raise BoojumError / ValueError.  There is no CPU fallback.
 """
-import ctypes
-
 import numpy as np
 
 from ._lib import call
-from .field import as_u64_host, col_view, stream_of
-
-_u64p = ctypes.POINTER(ctypes.c_uint64)
-
-
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
+from .field import as_u64_host, col_view, host_ptr, log2_exact, stream_of
 
 
 # ---------------------------------------------------------------- device forms
@@ -34,7 +24,7 @@ def precompute_twiddles_for_fft(fft_size, inverse=False, device=None):
     """precompute_twiddles_for_fft::<INVERSED> (utils.rs:88-125): omega^i (omega^-i),
     i < n/2, bit-reversed.  Returns an int64 CUDA tensor of n/2 u64."""
     import torch
-    log_n = _log2(fft_size)
+    log_n = log2_exact(fft_size)
     if log_n == 0:
         raise ValueError("twiddles need fft_size >= 2")
     out = torch.empty(fft_size // 2, dtype=torch.int64, device=device or "cuda")
@@ -45,7 +35,7 @@ def precompute_twiddles_for_fft(fft_size, inverse=False, device=None):
 def fft_natural_to_bitreversed(cols, coset=1, twiddles=None):
     """fft/mod.rs:398-411, in place on a (n,) or (C, n) int64 CUDA tensor."""
     v, c, n, stride = col_view(cols)
-    call("bj_fft_natural_to_bitreversed_d", v.data_ptr(), c, stride, _log2(n), int(coset),
+    call("bj_fft_natural_to_bitreversed_d", v.data_ptr(), c, stride, log2_exact(n), int(coset),
          twiddles.data_ptr() if twiddles is not None else None, stream_of(v))
     return cols
 
@@ -53,7 +43,7 @@ def fft_natural_to_bitreversed(cols, coset=1, twiddles=None):
 def ifft_natural_to_natural(cols, coset=1, twiddles=None):
     """fft/mod.rs:464-491, in place."""
     v, c, n, stride = col_view(cols)
-    call("bj_ifft_natural_to_natural_d", v.data_ptr(), c, stride, _log2(n), int(coset),
+    call("bj_ifft_natural_to_natural_d", v.data_ptr(), c, stride, log2_exact(n), int(coset),
          twiddles.data_ptr() if twiddles is not None else None, stream_of(v))
     return cols
 
@@ -61,7 +51,7 @@ def ifft_natural_to_natural(cols, coset=1, twiddles=None):
 def distribute_powers(cols, element):
     """fft/mod.rs:308-317, in place: col[j] *= element^j."""
     v, c, n, stride = col_view(cols)
-    call("bj_distribute_powers_d", v.data_ptr(), c, stride, _log2(n), int(element), stream_of(v))
+    call("bj_distribute_powers_d", v.data_ptr(), c, stride, log2_exact(n), int(element), stream_of(v))
     return cols
 
 
@@ -69,7 +59,7 @@ def precompute_twiddles_for_fft_natural(fft_size, inverse=False, device=None):
     """precompute_twiddles_for_fft_natural::<INVERSED> (utils.rs:127-155, fft/mod.rs:640-657):
     omega^i (omega^-i), i < n/2, natural order.  int64 CUDA tensor of n/2 u64."""
     import torch
-    log_n = _log2(fft_size)
+    log_n = log2_exact(fft_size)
     if log_n == 0:
         raise ValueError("twiddles need fft_size >= 2")
     out = torch.empty(fft_size // 2, dtype=torch.int64, device=device or "cuda")
@@ -80,7 +70,7 @@ def precompute_twiddles_for_fft_natural(fft_size, inverse=False, device=None):
 def bitreverse_enumeration_inplace(cols):
     """fft/mod.rs:41-155: bit-reversal permutation of each column, in place."""
     v, c, n, stride = col_view(cols)
-    call("bj_bitreverse_enumeration_d", v.data_ptr(), c, stride, _log2(n), stream_of(v))
+    call("bj_bitreverse_enumeration_d", v.data_ptr(), c, stride, log2_exact(n), stream_of(v))
     return cols
 
 
@@ -99,33 +89,29 @@ precompute_twiddles_for_fft_natural_wrapper = precompute_twiddles_for_fft_natura
 
 # ------------------------------------------------------------------ host forms
 
-def _hp(a):
-    return a.ctypes.data_as(_u64p)
-
-
 def precompute_twiddles_for_fft_host(fft_size, inverse=False):
-    log_n = _log2(fft_size)
+    log_n = log2_exact(fft_size)
     out = np.zeros(fft_size // 2, dtype=np.uint64)
-    call("bj_precompute_twiddles_h", log_n, 1 if inverse else 0, _hp(out))
+    call("bj_precompute_twiddles_h", log_n, 1 if inverse else 0, host_ptr(out))
     return out
 
 
 def fft_natural_to_bitreversed_host(col, coset=1):
     a = as_u64_host(col)
-    _log2(a.size)
-    call("bj_fft_natural_to_bitreversed_h", _hp(a), a.size, int(coset))
+    log2_exact(a.size)
+    call("bj_fft_natural_to_bitreversed_h", host_ptr(a), a.size, int(coset))
     return a
 
 
 def ifft_natural_to_natural_host(col, coset=1):
     a = as_u64_host(col)
-    _log2(a.size)
-    call("bj_ifft_natural_to_natural_h", _hp(a), a.size, int(coset))
+    log2_exact(a.size)
+    call("bj_ifft_natural_to_natural_h", host_ptr(a), a.size, int(coset))
     return a
 
 
 def distribute_powers_host(col, element):
     a = as_u64_host(col)
-    _log2(a.size)
-    call("bj_distribute_powers_h", _hp(a), a.size, int(element))
+    log2_exact(a.size)
+    call("bj_distribute_powers_h", host_ptr(a), a.size, int(element))
     return a

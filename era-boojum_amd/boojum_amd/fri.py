@@ -22,21 +22,7 @@ import torch
 
 from ._lib import call
 from .fft import bitreverse_enumeration_inplace, ifft_natural_to_natural
-from .field import GENERATOR, P, stream_of, to_host
-
-EXT2_NON_RESIDUE = 7   # GoldilocksExt2::NON_RESIDUE (field/goldilocks/extension.rs:14-16)
-
-
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
-
-
-def ext2_square(a):
-    """(a0 + a1 u)^2 with u^2 = 7 (field/traits/field.rs:427-440), on host ints."""
-    a0, a1 = a
-    return ((a0 * a0 + EXT2_NON_RESIDUE * a1 * a1) % P, (2 * a0 * a1) % P)
+from .field import GENERATOR, P, ext2_square, log2_exact, stream_of, to_host
 
 
 def challenge_powers(challenge, reduction_degree_log_2):
@@ -49,7 +35,7 @@ def challenge_powers(challenge, reduction_degree_log_2):
 
 def precompute_roots(full_size, device="cuda"):
     """precompute_twiddles_for_fft::<INVERSED = true>(full_size) (fri/mod.rs:191-192)."""
-    log_n = _log2(full_size)
+    log_n = log2_exact(full_size)
     out = torch.empty((full_size // 2,), dtype=torch.int64, device=device)
     call("bj_precompute_twiddles_d", log_n, 1, out.data_ptr(), stream_of(out))
     return out
@@ -201,7 +187,7 @@ def do_fri(c0, c1, transcript, interpolation_log2s_schedule, lde_degree, cap_siz
             raise ValueError("a folding step of %d is outside 1..3 (fri/mod.rs:204-205)" % s)
     rows = _paired_rows(c0, c1)
     full_size = rows.shape[1]
-    log_full, log_lde = _log2(full_size), _log2(lde_degree)
+    log_full, log_lde = log2_exact(full_size), log2_exact(lde_degree)
     if log_lde > log_full or (full_size // lde_degree) >> sum(schedule) == 0:
         raise ValueError("final_degree is 0 (fri/mod.rs:82)")
     log_n = log_full - log_lde

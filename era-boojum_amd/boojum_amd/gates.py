@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from ._lib import call, load
-from .field import P, stream_of, to_device, to_host
+from .field import P, log2_exact, new_status, read_status, stream_of, to_device
 
 MAX_SLOTS = 16              # BJ_GATE_MAX_SLOTS
 MAX_SELECTOR_DEPTH = 8      # BJ_GATE_MAX_SELECTOR_DEPTH
@@ -518,12 +518,6 @@ class GateSet:
             pass
 
 
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
-
-
 def _lde(t, q, what):
     """(data pointer, column stride, columns, n) of a (C, D, n) LDE, or zeros for None."""
     if t is None:
@@ -553,7 +547,7 @@ def evaluate_gate_terms(gate_set, variables_lde, witnesses_lde, constants_lde, a
     one the set never names may be None.  alphas: the set's Ext2 challenge powers, a list of
     (c0, c1) pairs (copied to the device here) or a (K, 2) device tensor (read in place, so a
     captured graph sees later contents).  dst_c0, dst_c1: q * n words each."""
-    log_q = _log2(quotient_degree)
+    log_q = log2_exact(quotient_degree)
     v, v_stride, n_v, n1 = _lde(variables_lde, quotient_degree, "variables_lde")
     w, w_stride, n_w, n2 = _lde(witnesses_lde, quotient_degree, "witnesses_lde")
     c, c_stride, n_c, n3 = _lde(constants_lde, quotient_degree, "constants_lde")
@@ -572,7 +566,7 @@ def evaluate_gate_terms(gate_set, variables_lde, witnesses_lde, constants_lde, a
         raise ValueError("alphas: a contiguous (K, 2) int64 device tensor")
     for segment in range(gate_set.num_segments):
         call("bj_quotient_gate_terms_d", gate_set._handle, segment, v, v_stride, n_v, w, w_stride, n_w, c, c_stride,
-             n_c, alphas.data_ptr(), alphas.shape[0], _log2(n), log_q, dst_c0.data_ptr(), dst_c1.data_ptr(),
+             n_c, alphas.data_ptr(), alphas.shape[0], log2_exact(n), log_q, dst_c0.data_ptr(), dst_c1.data_ptr(),
              stream_of(dst_c0))
 
 
@@ -656,14 +650,14 @@ def check_if_satisfied(gate_set, variables, witnesses, constants, rows=None, sta
         raise ValueError("rows (%d, %d): a window of at least one row inside the %d of the trace" % (begin, count, n))
     first = next(t for t in (variables, witnesses, constants) if t is not None)
     if status is None:
-        status = torch.empty((4,), dtype=torch.int64, device=first.device)
+        status = new_status(first.device)
     elif not status.is_cuda or status.dtype not in (torch.int64, torch.uint64) or status.numel() != 4 \
             or not status.is_contiguous():
         raise ValueError("status: 4 contiguous int64 words on the device")
     for segment in range(gate_set.num_segments):
         call("bj_gate_set_satisfied_d", gate_set._handle, segment | (CHECK_BEGIN if segment == 0 else 0), v, v_stride,
              n_v, w, w_stride, n_w, c, c_stride, n_c, begin, count, status.data_ptr(), stream_of(first))
-    return report_from_status(gate_set, [int(x) for x in to_host(status)])
+    return report_from_status(gate_set, read_status(status))
 
 
 # ------------------------------------------------------------------ evaluators

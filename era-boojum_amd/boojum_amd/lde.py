@@ -10,7 +10,7 @@ lde[c].reshape(-1).
 import torch
 
 from ._lib import call
-from .field import col_view, stream_of
+from .field import col_view, log2_exact, stream_of
 
 
 def lde_coset(log_n, log_d, i):
@@ -23,19 +23,13 @@ def lde_coset(log_n, log_d, i):
     return pow(g, r, P) * GENERATOR % P
 
 
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
-
-
 def transform_raw_storages_to_lde(trace, lde_degree, scratch=None, out=None):
     """utils.rs:270-309 + transform_monomials_to_lde :311-403 for a (C, n) int64 CUDA
     tensor.  Returns lde (C, D, n) (the reference returns only the LDE storages; the
     monomials are consumed).  `scratch` (C, n) / `out` may be preallocated buffers
     (reused across calls by a batched prover)."""
     v, c, n, stride = col_view(trace)
-    log_n, log_d = _log2(n), _log2(lde_degree)
+    log_n, log_d = log2_exact(n), log2_exact(lde_degree)
     if log_d == 0:
         raise ValueError("lde_degree must be > 1 (utils.rs:283)")
     if scratch is None:
@@ -50,7 +44,7 @@ def transform_raw_storages_to_lde(trace, lde_degree, scratch=None, out=None):
 def transform_monomials_to_lde(monomials, lde_degree, out=None):
     """utils.rs:311-403 (also the quotient commit, prover.rs:1471-1482)."""
     v, c, n, stride = col_view(monomials)
-    log_n, log_d = _log2(n), _log2(lde_degree)
+    log_n, log_d = log2_exact(n), log2_exact(lde_degree)
     if log_d == 0:
         raise ValueError("lde_degree must be > 1 (utils.rs:283)")
     if out is None:

@@ -12,19 +12,11 @@ Device layout: leaf_hashes (n_leaves, 4); node levels concatenated from the leav
 to the cap, (n_leaves - cap_size, 4) -- the reference's node_hashes_enumerated_from_leafs
 as one buffer (level l starts at sum_{i<l} n_leaves / 2^(i+1)).
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from ._lib import call
-from .field import as_u64_host, stream_of, to_host
-
-_u64p = ctypes.POINTER(ctypes.c_uint64)
-
-
-def _hp(a):
-    return a.ctypes.data_as(_u64p)
+from .field import as_u64_host, host_ptr, log2_exact, stream_of, to_host
 
 
 def _tree_hasher(name, doc, f_leaf, f_node):
@@ -35,12 +27,12 @@ def _tree_hasher(name, doc, f_leaf, f_node):
     def hash_into_leaf(elements):
         e = as_u64_host(elements)
         out = np.zeros(4, dtype=np.uint64)
-        call(f_leaf, _hp(e) if e.size else None, e.size, _hp(out))
+        call(f_leaf, host_ptr(e) if e.size else None, e.size, host_ptr(out))
         return out
 
     def hash_into_node(left, right, depth=0):
         out = np.zeros(4, dtype=np.uint64)
-        call(f_node, _hp(as_u64_host(left)), _hp(as_u64_host(right)), _hp(out))
+        call(f_node, host_ptr(as_u64_host(left)), host_ptr(as_u64_host(right)), host_ptr(out))
         return out
 
     def digest_bytes(words):
@@ -75,7 +67,7 @@ def _poseidon2_permutation(state):
     s = as_u64_host(state).copy()
     if s.size != 12:
         raise ValueError("state must have 12 elements")
-    call("bj_poseidon2_permute_h", _hp(s))
+    call("bj_poseidon2_permute_h", host_ptr(s))
     return s
 
 
@@ -86,12 +78,6 @@ def _hasher(name):
     if name not in HASHERS:
         raise ValueError("unknown tree hasher %r (expected one of %s)" % (name, sorted(HASHERS)))
     return HASHERS[name]
-
-
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
 
 
 def _leaf_sources(leafs_sources, num_cosets=None):
@@ -127,8 +113,8 @@ class MerkleTreeWithCap:
     def construct(cls, leafs_sources, cap_size, num_cosets=None, leaf_out=None, node_out=None, hasher="poseidon2"):
         f_leaves, f_nodes = _hasher(hasher)[1], _hasher(hasher)[3]
         src, c, stride, nl = _leaf_sources(leafs_sources, num_cosets)
-        _log2(nl)
-        _log2(cap_size)
+        log2_exact(nl)
+        log2_exact(cap_size)
         if nl <= cap_size:
             raise ValueError("tree size must exceed cap size (merkle_tree.rs:97)")
         dev = src.device
@@ -146,8 +132,8 @@ class MerkleTreeWithCap:
         in order). leafs_sources: (C, D, n) LDE tensor or (C, L) flat rows."""
         src, c, stride, total = _leaf_sources(leafs_sources)
         e = elements_to_take_per_leaf
-        _log2(e)
-        _log2(cap_size)
+        log2_exact(e)
+        log2_exact(cap_size)
         if total % e:
             raise ValueError("source length must be a multiple of elements_to_take_per_leaf")
         nl = total // e
@@ -165,8 +151,8 @@ class MerkleTreeWithCap:
         cap is then the leaf layer)."""
         src, c, stride, total = _leaf_sources(leafs_sources)
         e = elements_to_take_per_leaf
-        _log2(e)
-        _log2(cap_size)
+        log2_exact(e)
+        log2_exact(cap_size)
         if total % e:
             raise ValueError("poly size must be a multiple of elements_to_take_per_leaf")
         nl = total // e
@@ -177,7 +163,7 @@ class MerkleTreeWithCap:
     @classmethod
     def _chunked(cls, src, c, stride, nl, e, cap_size, hasher):
         f_chunked, f_nodes = _hasher(hasher)[2:4]
-        _log2(nl)
+        log2_exact(nl)
         dev = src.device
         leaves = torch.empty((nl, 4), dtype=torch.int64, device=dev)
         nodes = torch.empty((nl - cap_size, 4), dtype=torch.int64, device=dev)
@@ -192,7 +178,7 @@ class MerkleTreeWithCap:
         return self.leaf_hashes.shape[0]
 
     def num_levels(self):
-        return _log2(self.n_leaves) - _log2(self.cap_size)
+        return log2_exact(self.n_leaves) - log2_exact(self.cap_size)
 
     def level(self, l):
         """Node level l (1 = parents of the leaves), as a device tensor view."""

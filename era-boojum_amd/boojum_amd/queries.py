@@ -22,14 +22,7 @@ import numpy as np
 
 from ._lib import QUERY_MAX_ORACLES, BoojumError, QueryOracleDesc, call
 from . import serialization
-
-STATUS_WORDS = 4
-
-
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
+from .field import STATUS_WORDS, log2_exact
 
 
 # ------------------------------------------------------------------ layout (host arithmetic only)
@@ -56,8 +49,8 @@ def fri_plan(log_n, log_lde, schedule):
 def query_words(n_cols, elements_per_leaf, n_leaves, cap_size):
     """bj_oracle_query_words: the leaf's n_cols * elements_per_leaf elements, the leaf hash, and
     4 words for each of the log2(n_leaves / cap_size) siblings."""
-    _log2(elements_per_leaf)
-    depth = _log2(n_leaves) - _log2(cap_size)
+    log2_exact(elements_per_leaf)
+    depth = log2_exact(n_leaves) - log2_exact(cap_size)
     if depth < 0:
         raise ValueError("n_leaves < cap_size")
     return n_cols * elements_per_leaf + 4 + 4 * depth
@@ -107,7 +100,7 @@ class QueryOracle:
         from .merkle import _leaf_sources
         self.tree, self.sources = tree, sources
         self.elements_per_leaf, self.index_shift = elements_per_leaf, index_shift
-        self.log_e = _log2(elements_per_leaf)
+        self.log_e = log2_exact(elements_per_leaf)
         self.n_leaves, self.cap_size = tree.n_leaves, tree.cap_size
         self.n_cols, self.col_stride, self._src = 0, 0, None
         if sources is not None:
@@ -118,7 +111,7 @@ class QueryOracle:
             if src.device != tree.leaf_hashes.device:
                 raise ValueError("sources and tree are on different devices")
             self.n_cols, self.col_stride, self._src = c, stride, src
-        self.depth = _log2(self.n_leaves) - _log2(self.cap_size)
+        self.depth = log2_exact(self.n_leaves) - log2_exact(self.cap_size)
         self.n_elements = self.n_cols * elements_per_leaf
         self.words = query_words(self.n_cols, elements_per_leaf, self.n_leaves, self.cap_size)
 
@@ -189,10 +182,10 @@ class OracleQuery(namedtuple("OracleQuery", "leaf_elements proof")):
         holds row inner_idx of coset coset_idx, num_elements values of every column of `source` per
         leaf; tree index (coset_idx << (log2 domain_size - log2 num_elements)) + inner_idx /
         num_elements.  A batch of one."""
-        _log2(domain_size)
+        log2_exact(domain_size)
         if not 0 <= coset_idx < lde_factor or not 0 <= inner_idx < domain_size:
             raise ValueError("coset_idx or inner_idx out of range")
-        o = QueryOracle(tree, source, num_elements, _log2(num_elements))
+        o = QueryOracle(tree, source, num_elements, log2_exact(num_elements))
         r = construct_queries([o], [coset_idx * domain_size + inner_idx])[0]
         return cls(r.leaf_elements[0], r.proof[0])
 

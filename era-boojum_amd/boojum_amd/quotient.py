@@ -22,18 +22,11 @@ import ctypes
 import torch
 
 from ._lib import call
-from .deep import ext2_mul
 from .fft import bitreverse_enumeration_inplace, ifft_natural_to_natural
-from .field import GENERATOR, P, stream_of, to_host
+from .field import GENERATOR, P, ext2_mul, log2_exact, stream_of, to_host
 from .stage2 import MAX_LOOKUP_SOURCES, non_residues_for_copy_permutation
 
 MAX_QUOTIENT_DEGREE = 128  # BJ_QUOTIENT_MAX_DEGREE
-
-
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
 
 
 def _lde_view(t, q):
@@ -74,7 +67,7 @@ def compute_quotient_terms_in_extension(variables_lde, sigmas_lde, second_stage_
     second_stage_lde: the LDE of the stage-2 columns, whose first 2 m columns are z and the
     intermediates (stage2.SecondStageTrace's order); alphas: m + 1 Ext2 challenges, the L_1 term's
     first (the reference takes that one at prover.rs:1180 and the other m at :1241-1250)."""
-    log_q = _log2(quotient_degree)
+    log_q = log2_exact(quotient_degree)
     v, c, n, v_stride = _lde_view(variables_lde, quotient_degree)
     s, c2, n2, s_stride = _lde_view(sigmas_lde, quotient_degree)
     z, c3, n3, z_stride = _lde_view(second_stage_lde, quotient_degree)
@@ -85,7 +78,7 @@ def compute_quotient_terms_in_extension(variables_lde, sigmas_lde, second_stage_
         raise ValueError("the stage-2 LDE needs the 2 m = %d copy-permutation columns, got %d" % (2 * m, c3))
     if len(alphas) != m + 1:
         raise ValueError("expected m + 1 = %d challenges, got %d" % (m + 1, len(alphas)))
-    log_n = _log2(n)
+    log_n = log2_exact(n)
     total = n * quotient_degree
     _acc_view(dst_c0, total), _acc_view(dst_c1, total)
     k = non_residues_for_copy_permutation(n, c)
@@ -99,7 +92,7 @@ def lookup_term(sources, coefficients, beta, encoding, alpha, quotient_degree, d
     """dst += alpha (E (beta + sum_t coefficients[t] sources[t]) - f) (bj_quotient_lookup_term_d):
     sources are up to 16 LDE columns (D, n) of any tensors, encoding the (c0, c1) pair of LDE
     columns of E, f an LDE column or None for 1."""
-    log_q = _log2(quotient_degree)
+    log_q = log2_exact(quotient_degree)
     if not 1 <= len(sources) <= MAX_LOOKUP_SOURCES:
         raise ValueError("1..%d source columns, got %d" % (MAX_LOOKUP_SOURCES, len(sources)))
     if len(coefficients) != len(sources):
@@ -114,7 +107,7 @@ def lookup_term(sources, coefficients, beta, encoding, alpha, quotient_degree, d
     g = (ctypes.c_uint64 * (2 * len(sources)))(*[limb % P for pair in coefficients for limb in pair])
     e0, e1 = cols[len(sources)][0], cols[len(sources) + 1][0]
     call("bj_quotient_lookup_term_d", ptrs, len(sources), g, beta[0] % P, beta[1] % P, e0.data_ptr(), e1.data_ptr(),
-         cols[-1][0].data_ptr() if f is not None else None, alpha[0] % P, alpha[1] % P, _log2(n), log_q,
+         cols[-1][0].data_ptr() if f is not None else None, alpha[0] % P, alpha[1] % P, log2_exact(n), log_q,
          dst_c0.data_ptr(), dst_c1.data_ptr(), stream_of(dst_c0))
 
 
@@ -155,7 +148,7 @@ def compute_quotient_terms_for_lookup_specialized(variables_lde, multiplicities_
 
 def divide_by_vanishing_for_bitreversed_coset_enumeration(dst_c0, dst_c1, log_n):
     """utils.rs:770-817 on both halves of the accumulator (q * n words each), in place."""
-    log_q = _log2(dst_c0.numel()) - log_n
+    log_q = log2_exact(dst_c0.numel()) - log_n
     if log_q < 0:
         raise ValueError("the accumulator is shorter than one coset")
     _acc_view(dst_c1, dst_c0.numel())
@@ -176,7 +169,7 @@ def quotient_monomials(dst_c0, dst_c1, log_n):
     q = total // n
     if q * n != total:
         raise ValueError("the accumulator is no multiple of a coset")
-    _log2(q)
+    log2_exact(q)
     halves = torch.stack([_acc_view(dst_c0, total).reshape(-1), _acc_view(dst_c1, total).reshape(-1)])
     if total > 1:
         bitreverse_enumeration_inplace(halves)
@@ -229,5 +222,5 @@ def quotient_from_arguments(variables_lde, sigmas_lde, second_stage_lde, beta, g
         used += reps + n_mult
     if used != len(challenges):
         raise ValueError("must exhaust all the challenges (prover.rs:1364): %d given, %d used" % (len(challenges), used))
-    divide_by_vanishing_for_bitreversed_coset_enumeration(dst_c0, dst_c1, _log2(n))
-    return quotient_monomials(dst_c0, dst_c1, _log2(n))
+    divide_by_vanishing_for_bitreversed_coset_enumeration(dst_c0, dst_c1, log2_exact(n))
+    return quotient_monomials(dst_c0, dst_c1, log2_exact(n))

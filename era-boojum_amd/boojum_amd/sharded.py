@@ -28,22 +28,16 @@ import ctypes
 import torch
 
 from ._lib import EXCHANGE_FN as _EXCHANGE_FN, call, check, load
-from .field import stream_of
+from .field import log2_exact, stream_of
 
 HASHER_IDS = {"poseidon2": 0, "blake2s": 1, "keccak256": 2}
 XCHG_ALL_GATHER, XCHG_ALL_TO_ALL = 0, 1   # bj_exchange_fn kinds (include/boojum_mi355x.h)
 
 
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
-
-
 def native_columns(n_cols, world, rank, hasher="poseidon2"):
     """bj_sharded_columns: the global trace columns rank `rank` of `world` holds, in the order of
     its trace-shard rows.  Host logic only (no device call)."""
-    log_g = _log2(world)
+    log_g = log2_exact(world)
     out = (ctypes.c_uint32 * (n_cols // world if n_cols % world == 0 and n_cols else 1))()
     check(load().bj_sharded_columns(n_cols, log_g, rank, HASHER_IDS[hasher], out), "bj_sharded_columns")
     return list(out)
@@ -273,7 +267,7 @@ def native_sharded_query(comm, res, n_cols, log_n, log_lde, cap_size, tree_idx, 
     (leaf_elements (C,), leaf_hash (4,), proof (depth, 4)) as numpy uint64."""
     import numpy as np
     log_k = log_lde if log_commit_cosets is None else log_commit_cosets
-    depth = (log_n + log_k) - _log2(cap_size)
+    depth = (log_n + log_k) - log2_exact(cap_size)
     elems = np.zeros(n_cols, dtype=np.uint64)
     leaf = np.zeros(4, dtype=np.uint64)
     proof = np.zeros((max(depth, 1), 4), dtype=np.uint64)
@@ -295,7 +289,7 @@ class ShardedQueryOracle:
         log_k = log_lde if log_commit_cosets is None else log_commit_cosets
         self.res, self.hasher = res, hasher
         self.n_leaves, self.cap_size = 1 << (log_n + log_k), cap_size
-        self.depth = (log_n + log_k) - _log2(cap_size)
+        self.depth = (log_n + log_k) - log2_exact(cap_size)
         self.n_cols = self.n_elements = n_cols if sources else 0
         self.col_stride = res.lde.stride(1) if sources else 0
         self.words = self.n_cols + 4 + 4 * self.depth

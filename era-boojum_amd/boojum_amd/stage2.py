@@ -21,8 +21,7 @@ from collections import namedtuple
 import torch
 
 from ._lib import BoojumError, call
-from .deep import ext2_mul
-from .field import P, col_view, stream_of, to_host
+from .field import P, col_view, ext2_mul, log2_exact, new_status, read_status, stream_of
 
 # LookupParameters::UseSpecializedColumnsWithTableIdAsVariable / ...AsConstant
 # (lookup_argument_in_ext.rs:353-383): kind is "variable" or "constant"
@@ -31,17 +30,11 @@ LookupParameters = namedtuple("LookupParameters", "kind width num_repetitions")
 MAX_LOOKUP_SOURCES = 16
 
 
-def _log2(n):
-    if n <= 0 or n & (n - 1):
-        raise ValueError("size must be a power of two, got %d" % n)
-    return n.bit_length() - 1
-
-
 def non_residues_for_copy_permutation(domain_size, num_columns):
     """copy_permutation.rs:512-522: [1] + make_non_residues(num_columns - 1, domain_size)
     (utils.rs:636-688), as Python integers.  Host only."""
     out = (ctypes.c_uint64 * num_columns)()
-    call("bj_non_residues_h", num_columns, _log2(domain_size), out)
+    call("bj_non_residues_h", num_columns, log2_exact(domain_size), out)
     return [int(v) for v in out]
 
 
@@ -50,15 +43,6 @@ def num_intermediate_partial_product_relations(num_cols, quotient_degree):
     if num_cols <= quotient_degree:
         return 0
     return (num_cols + quotient_degree - 1) // quotient_degree - 1
-
-
-def _status(device):
-    return torch.zeros((4,), dtype=torch.int64, device=device)
-
-
-def _read_status(status):
-    s = to_host(status)
-    return (int(s[0]), int(s[1])), int(s[2])
 
 
 def _pairs(t):
@@ -86,8 +70,8 @@ def compute_partial_products_in_extension(variables, sigmas, beta, gamma, max_de
     s, c2, n2, s_stride = col_view(sigmas)
     if (c, n) != (c2, n2):
         raise ValueError("variables and sigmas shapes differ")
-    log_n = _log2(n)
-    _log2(max_degree)
+    log_n = log2_exact(n)
+    log2_exact(max_degree)
     m = (c + max_degree - 1) // max_degree
     if out is None:
         out = torch.empty((2 * m, n), dtype=torch.int64, device=v.device)
@@ -95,13 +79,14 @@ def compute_partial_products_in_extension(variables, sigmas, beta, gamma, max_de
     if (oc, on) != (2 * m, n):
         raise ValueError("out must be (%d, %d), got (%d, %d)" % (2 * m, n, oc, on))
     k = non_residues_for_copy_permutation(n, c)
-    status = _status(v.device)
+    status = new_status(v.device)
     call("bj_copy_permutation_d", v.data_ptr(), v_stride, s.data_ptr(), s_stride, c, log_n,
          (ctypes.c_uint64 * c)(*k), beta[0] % P, beta[1] % P, gamma[0] % P, gamma[1] % P, max_degree, o.data_ptr(),
          o_stride, status.data_ptr(), stream_of(v))
     compute_partial_products_in_extension.status = status
     if check:
-        total, zeros = _read_status(status)
+        t0, t1, zeros, _ = read_status(status)
+        total = (t0, t1)
         if zeros:
             raise BoojumError("copy permutation: %d zero denominator(s)" % zeros)
         if total != (1, 0):
@@ -123,12 +108,12 @@ def lookup_encoding(sources, coefficients, beta, out_c0, out_c1, f=None, status=
     if any(t.shape != (1, n) for t in cols):
         raise ValueError("every column must have %d rows" % n)
     if status is None:
-        status = _status(out_c0.device)
+        status = new_status(out_c0.device)
     ptrs = (ctypes.c_void_p * len(sources))(*[t.data_ptr() for t in cols[:len(sources)]])
     g = (ctypes.c_uint64 * (2 * len(sources)))(*[limb % P for pair in coefficients for limb in pair])
     call("bj_lookup_encoding_d", ptrs, len(sources), g, beta[0] % P, beta[1] % P,
-         f.data_ptr() if f is not None else None, _log2(n), out_c0.data_ptr(), out_c1.data_ptr(), status.data_ptr(),
-         stream_of(out_c0))
+         f.data_ptr() if f is not None else None, log2_exact(n), out_c0.data_ptr(), out_c1.data_ptr(),
+         status.data_ptr(), stream_of(out_c0))
     return status
 
 
@@ -181,7 +166,7 @@ def compute_lookup_poly_pairs_specialized(variables_columns, multiplicities_colu
         statuses.append(lookup_encoding(tables, powers, beta, *pairs[p.num_repetitions + i],
                                         f=multiplicities_columns[i]))
     if check:
-        zeros = sum(_read_status(st)[1] for st in statuses)
+        zeros = sum(read_status(st)[2] for st in statuses)
         if zeros:
             raise BoojumError("lookup encodings: %d zero denominator(s)" % zeros)
     return pairs[:p.num_repetitions], pairs[p.num_repetitions:]

@@ -14,12 +14,10 @@
 // Field arithmetic is exact, so any order of operations gives the reference's bits once the
 // outputs are canonical.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include "gl.hpp"
 #include "gl_asm.hpp"
 #include "ext2.hpp"
-#include "bj_internal.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "stage_host.hpp"
 
 namespace bj {
 
@@ -254,24 +252,6 @@ __global__ __launch_bounds__(256) void deep_quotient_kernel(
 }
 
 // ------------------------------------------------------------------ launchers
-struct Ext2 {
-    uint64_t c0, c1;
-};
-Ext2 ext_mul(Ext2 a, Ext2 b) {
-    return {gl::add(gl::mul(a.c0, b.c0), times7(gl::mul(a.c1, b.c1))), gl::add(gl::mul(a.c0, b.c1), gl::mul(a.c1, b.c0))};
-}
-
-// stream-ordered scratch from the library's pool, freed on the same stream when it goes out of scope
-struct Scratch {
-    uint64_t* p = nullptr;
-    hipStream_t st;
-    explicit Scratch(hipStream_t s) : st(s) {}
-    hipError_t alloc(size_t words) { return pool_alloc((void**)&p, words * 8, st); }
-    ~Scratch() {
-        if (p) (void)hipFreeAsync(p, st);
-    }
-};
-
 hipError_t launch_pow_table(uint64_t* tab, uint64_t w, uint64_t scale, hipStream_t st) {
     hipLaunchKernelGGL(pow_table_kernel, dim3(POW_TAB_WORDS / 256), dim3(256), 0, st, tab, w, scale);
     return hipGetLastError();
@@ -286,10 +266,10 @@ hipError_t launch_weights(uint32_t log_n, uint64_t coset, uint64_t at0, uint64_t
     const size_t n = (size_t)1 << log_n;
     // C' = (at^n - coset^n) / (n coset^n) (utils.rs:933-945 without the factor coset, which the kernel's y carries)
     coset = gl::canon(coset);
-    Ext2 an{gl::canon(at0), gl::canon(at1)};
+    E2 an = canon2(at0, at1);
     uint64_t cn = coset;
     for (uint32_t i = 0; i < log_n; i++) {
-        an = ext_mul(an, an);
+        an = mul(an, an);
         cn = gl::mul(cn, cn);
     }
     const uint64_t k = gl::inv(gl::mul(cn, gl::canon((uint64_t)n)));
@@ -348,12 +328,6 @@ hipError_t launch_deep_quotient(const uint64_t* cols, uint32_t n_cols, size_t co
     return hipGetLastError();
 }
 
-int hip_error(hipError_t e, const char* what) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-    return set_error(BJ_EHIP, msg);
-}
-
 }  // namespace
 
 }  // namespace bj
@@ -362,22 +336,21 @@ extern "C" {
 
 int bj_barycentric_weights_d(uint32_t log_n, uint64_t coset, uint64_t at0, uint64_t at1, uint64_t* w0, uint64_t* w1,
                              void* stream) {
-    if (log_n > 32) return bj::set_error(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
+    if (const char* why = bj::bad_log_n(log_n)) return bj::set_error(BJ_EINVAL, why);
     if (!w0 || !w1) return bj::set_error(BJ_EINVAL, "bj_barycentric_weights_d: null output");
     if (gl::canon(coset) == 0) return bj::set_error(BJ_EINVAL, "bj_barycentric_weights_d: coset must be non-zero");
-    const hipError_t e = bj::launch_weights(log_n, coset, at0, at1, w0, w1, reinterpret_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "barycentric weights");
+    const hipError_t e = bj::launch_weights(log_n, coset, at0, at1, w0, w1, bj::stream_of(stream));
+    return bj::ok_or(e, "barycentric weights");
 }
 
 int bj_evaluate_at_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride, uint32_t log_n, const uint64_t* w0,
                      const uint64_t* w1, uint64_t* out, void* stream) {
-    if (log_n > 32) return bj::set_error(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
+    if (const char* why = bj::bad_log_n(log_n)) return bj::set_error(BJ_EINVAL, why);
     if (n_cols == 0) return BJ_OK;
     if (!cols || !w0 || !w1 || !out) return bj::set_error(BJ_EINVAL, "bj_evaluate_at_d: null pointer");
     if (col_stride < ((size_t)1 << log_n)) return bj::set_error(BJ_EINVAL, "bj_evaluate_at_d: col_stride < 2^log_n");
-    const hipError_t e =
-        bj::launch_evaluate_at(cols, n_cols, col_stride, log_n, w0, w1, out, reinterpret_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "evaluate at");
+    const hipError_t e = bj::launch_evaluate_at(cols, n_cols, col_stride, log_n, w0, w1, out, bj::stream_of(stream));
+    return bj::ok_or(e, "evaluate at");
 }
 
 int bj_deep_quotient_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride, const uint64_t* gammas, uint64_t k0,
@@ -392,8 +365,8 @@ int bj_deep_quotient_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride,
     if (n_cols && (!cols || !gammas)) return bj::set_error(BJ_EINVAL, "bj_deep_quotient_d: null cols or gammas");
     if (n_cols && col_stride < n_rows) return bj::set_error(BJ_EINVAL, "bj_deep_quotient_d: col_stride < n_rows");
     const hipError_t e = bj::launch_deep_quotient(cols, n_cols, col_stride, gammas, k0, k1, at0, at1, log_domain, row0,
-                                                  n_rows, dst0, dst1, accumulate, reinterpret_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "deep quotient");
+                                                  n_rows, dst0, dst1, accumulate, bj::stream_of(stream));
+    return bj::ok_or(e, "deep quotient");
 }
 
 }  // extern "C"

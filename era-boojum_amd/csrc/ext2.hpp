@@ -1,6 +1,6 @@
 // GoldilocksExt2 = F[u] / (u^2 - 7) (field/goldilocks/extension.rs:14-40) on top of gl.hpp: what
-// deep.hip, stage2.hip and quotient.hip share.  Values are (c0, c1) pairs of u64 representatives, not
-// necessarily canonical; a kernel canonicalises what it writes.
+// fri.hip, deep.hip, stage2.hip and quotient.hip share.  Values are (c0, c1) pairs of u64
+// representatives, not necessarily canonical; a kernel canonicalises what it writes.
 #pragma once
 #include "gl.hpp"
 #if defined(__HIPCC__)
@@ -19,6 +19,8 @@ GL_FN uint64_t neg(uint64_t v) { return gl::sub(0, v); }
 struct E2 {
     uint64_t c0, c1;
 };
+// an element from two words of the C ABI, which need not be canonical
+GL_FN E2 canon2(uint64_t c0, uint64_t c1) { return {gl::canon(c0), gl::canon(c1)}; }
 // (a0 + a1 u)(b0 + b1 u) (field/traits/field.rs:407-424)
 GL_FN E2 mul(E2 a, E2 b) {
     return {gl::add(gl::mul(a.c0, b.c0), times7(gl::mul(a.c1, b.c1))), gl::add(gl::mul(a.c0, b.c1), gl::mul(a.c1, b.c0))};

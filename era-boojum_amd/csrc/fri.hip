@@ -13,24 +13,17 @@
 // bj_fri_fold_multi_d folds by 2^r (r = 1..3, the range do_fri allows, fri/mod.rs:204-205) in one
 // launch: the r by-2 steps of one reduction run on registers (fri_fold_multi_kernel).
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include "gl.hpp"
 #include "gl_asm.hpp"
-#include "bj_internal.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "ext2.hpp"
+#include "stage_host.hpp"
 
 namespace bj {
 
 namespace {
 
-constexpr uint64_t EXT2_NON_RESIDUE = 7;  // GoldilocksExt2::NON_RESIDUE (extension.rs:14-16)
-static_assert(EXT2_NON_RESIDUE == (1u << 3) - 1, "the fold multiplies by the non-residue as 2^3 v - v");
-
-__device__ __forceinline__ void halves(uint64_t x, uint32_t& lo, uint32_t& hi) {
-    lo = (uint32_t)x;
-    hi = (uint32_t)(x >> 32);
-}
-__device__ __forceinline__ uint64_t join(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
+// the non-residue 7, times7 and the halves lo32, hi32, u64_of
+using namespace ext2;
 
 // beta = alpha * coset_inverse (an Ext2 times a base element, folded on the host) and
 // bsum = beta0 + beta1, so each output costs six products: (d0, d1) * roots[i] (2), the Karatsuba
@@ -49,29 +42,23 @@ struct Beta {
     uint32_t b0l, b0h, b1l, b1h, bsl, bsh;
 };
 __device__ __forceinline__ Beta beta_halves(uint64_t beta0, uint64_t beta1, uint64_t bsum) {
-    Beta b;
-    halves(beta0, b.b0l, b.b0h);
-    halves(beta1, b.b1l, b.b1h);
-    halves(bsum, b.bsl, b.bsh);
-    return b;
+    return {lo32(beta0), hi32(beta0), lo32(beta1), hi32(beta1), lo32(bsum), hi32(bsum)};
 }
 __device__ __forceinline__ void fold_pair(uint64_t x0, uint64_t y0, uint64_t x1, uint64_t y1, uint64_t r,
                                           const Beta& b, uint64_t& o0, uint64_t& o1) {
-    uint32_t s0l, s0h, s1l, s1h, rl, rh;
-    halves(gl::sub(x0, y0), s0l, s0h);
-    halves(gl::sub(x1, y1), s1l, s1h);
-    halves(r, rl, rh);
+    const uint64_t s0 = gl::sub(x0, y0), s1 = gl::sub(x1, y1);
+    const uint32_t s0l = lo32(s0), s0h = hi32(s0), s1l = lo32(s1), s1h = hi32(s1), rl = lo32(r), rh = hi32(r);
     uint32_t a0l, a0h, a1l, a1h;
     glasm::mul_x2(s0l, s0h, rl, rh, a0l, a0h, s1l, s1h, rl, rh, a1l, a1h);
-    uint32_t sal, sah;
-    halves(gl::add(join(a0l, a0h), join(a1l, a1h)), sal, sah);
+    const uint64_t sa = gl::add(u64_of(a0l, a0h), u64_of(a1l, a1h));
+    const uint32_t sal = lo32(sa), sah = hi32(sa);
     // (a0 + a1 u) (beta0 + beta1 u), u^2 = 7 (field/traits/field.rs:407-424)
     uint32_t v0l, v0h, v1l, v1h, ml, mh;
     glasm::mul_x3(a0l, a0h, b.b0l, b.b0h, v0l, v0h, a1l, a1h, b.b1l, b.b1h, v1l, v1h, sal, sah, b.bsl, b.bsh, ml,
                   mh);
-    const uint64_t v0 = join(v0l, v0h), v1 = join(v1l, v1h);
-    const uint64_t e1 = gl::sub(gl::sub(join(ml, mh), v0), v1);
-    const uint64_t e0 = gl::add(v0, gl::sub(gl::mul_pow2_small(v1, 3), v1));  // v0 + 7 v1
+    const uint64_t v0 = u64_of(v0l, v0h), v1 = u64_of(v1l, v1h);
+    const uint64_t e1 = gl::sub(gl::sub(u64_of(ml, mh), v0), v1);
+    const uint64_t e0 = gl::add(v0, times7(v1));
     o0 = gl::canon(gl::add(gl::add(e0, x0), y0));
     o1 = gl::canon(gl::add(gl::add(e1, x1), y1));
 }
@@ -224,7 +211,7 @@ int bj_fri_fold_multi_d(const uint64_t* c0, const uint64_t* c1, size_t n_src, co
     if (!c0 || !c1 || !roots || !dst_c0 || !dst_c1) return bj::set_error(BJ_EINVAL, "bj_fri_fold_multi_d: null pointer");
     if (((uintptr_t)c0 | (uintptr_t)c1 | (uintptr_t)roots | (uintptr_t)dst_c0 | (uintptr_t)dst_c1) % 8)
         return bj::set_error(BJ_EINVAL, "bj_fri_fold_multi_d: a pointer is not 8-byte aligned");
-    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const hipStream_t st = bj::stream_of(stream);
     const size_t n_out = n_src >> log_fold;
     hipError_t e;
     if (log_fold == 1) {
@@ -235,9 +222,9 @@ int bj_fri_fold_multi_d(const uint64_t* c0, const uint64_t* c1, size_t n_src, co
                           : bj::launch_fold_multi<3>(c0, c1, n_out, roots, fb, dst_c0, dst_c1, st);
     }
     if (e == hipSuccess) return BJ_OK;
-    char msg[160];
-    snprintf(msg, sizeof msg, "fri fold by 2^%u: %s", log_fold, hipGetErrorString(e));
-    return bj::set_error(BJ_EHIP, msg);
+    char what[32];
+    snprintf(what, sizeof what, "fri fold by 2^%u", log_fold);
+    return bj::hip_error(e, what);
 }
 
 }  // extern "C"

@@ -47,11 +47,9 @@
 // cs/implementations/satisfiability_test.rs:15-353): gate_check_kernel below walks the programs over
 // trace rows and reports the count and the first failing (row, term) in a status record.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <new>
 #include "gl.hpp"
-#include "bj_internal.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "stage_host.hpp"
 
 namespace bj {
 
@@ -399,10 +397,27 @@ int check_image(const uint64_t* image, size_t words, Need& need, uint64_t* seg_o
     return BJ_OK;
 }
 
-int hip_error(hipError_t e, const char* what) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-    return set_error(BJ_EHIP, msg);
+// The three column kinds of a call as the kernels take them.  A kind the set names must be there,
+// wide enough and with a stride of at least `extent` (`below` in the entry point's message); a kind
+// no operand names is never read and points at `unused`, so no lane forms a null address.
+int bind_columns(const Need& need, const uint64_t* const (&p)[3], const size_t (&stride)[3], const uint32_t (&have)[3],
+                 uint64_t extent, const uint64_t* unused, const char* entry, const char* below, Cols& cols) {
+    static const char* const name[3] = {"variables", "witnesses", "constants"};
+    for (int k = 0; k < 3; k++) {
+        char msg[160];
+        if (need.cols[k] > have[k]) {
+            snprintf(msg, sizeof msg, "gate program: an operand reaches %s column %llu of %u", name[k],
+                     (unsigned long long)(need.cols[k] - 1), have[k]);
+            return set_error(BJ_EINVAL, msg);
+        }
+        if (need.cols[k] && (!p[k] || stride[k] < extent)) {
+            snprintf(msg, sizeof msg, "%s: %s are null or their stride is below %s", entry, name[k], below);
+            return set_error(BJ_EINVAL, msg);
+        }
+        cols.p[k] = need.cols[k] ? p[k] : unused;
+        cols.stride[k] = need.cols[k] ? stride[k] : 0;
+    }
+    return BJ_OK;
 }
 
 }  // namespace
@@ -452,7 +467,7 @@ int bj_gate_set_release(void* set) {
     s->magic = 0;
     const hipError_t e = hipFree(s->image_d);
     delete s;
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "gate set release");
+    return bj::ok_or(e, "gate set release");
 }
 
 int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* vars, size_t vars_stride,
@@ -462,39 +477,20 @@ int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* 
                              void* stream) {
     const bj::GateSet* s = static_cast<const bj::GateSet*>(set);
     if (!s || s->magic != bj::GT_MAGIC) return bj::set_error(BJ_EINVAL, "bj_quotient_gate_terms_d: not a gate set");
-    if (log_n > 32 || log_q > 32 || log_n + log_q > 32)
-        return bj::set_error(BJ_EINVAL, "log_n + log_q exceeds the 2-adicity (32) of the field");
+    if (const char* why = bj::bad_domain(log_n, log_q)) return bj::set_error(BJ_EINVAL, why);
     if (segment >= s->n_segments) return bj::set_error(BJ_EINVAL, "bj_quotient_gate_terms_d: no such segment");
     if (!alphas || !dst0 || !dst1) return bj::set_error(BJ_EINVAL, "bj_quotient_gate_terms_d: null pointer");
     const size_t total = (size_t)1 << (log_n + log_q);
-    const uint64_t* p[3] = {vars, wits, consts};
-    const size_t stride[3] = {vars_stride, wits_stride, consts_stride};
-    const uint32_t have[3] = {n_vars, n_wits, n_consts};
-    static const char* const name[3] = {"variables", "witnesses", "constants"};
-    bj::Cols cols;
-    for (int k = 0; k < 3; k++) {
-        char msg[160];
-        if (s->need.cols[k] > have[k]) {
-            snprintf(msg, sizeof msg, "gate program: an operand reaches %s column %llu of %u", name[k],
-                     (unsigned long long)(s->need.cols[k] - 1), have[k]);
-            return bj::set_error(BJ_EINVAL, msg);
-        }
-        if (s->need.cols[k] && (!p[k] || stride[k] < total)) {
-            snprintf(msg, sizeof msg, "bj_quotient_gate_terms_d: %s are null or their stride is below 2^(log_n + log_q)",
-                     name[k]);
-            return bj::set_error(BJ_EINVAL, msg);
-        }
-        // a kind no operand names is never read; point it at the accumulator so no lane forms a null address
-        cols.p[k] = s->need.cols[k] ? p[k] : dst0;
-        cols.stride[k] = s->need.cols[k] ? stride[k] : 0;
-    }
+    bj::Cols cols;  // an unused kind points at the accumulator
+    if (const int rc = bj::bind_columns(s->need, {vars, wits, consts}, {vars_stride, wits_stride, consts_stride},
+                                        {n_vars, n_wits, n_consts}, total, dst0, "bj_quotient_gate_terms_d",
+                                        "2^(log_n + log_q)", cols))
+        return rc;
     if (s->need.alphas > n_alphas) return bj::set_error(BJ_EINVAL, "gate program: fewer challenges than terms");
     const size_t blocks = (total + bj::GT_THREADS - 1) / bj::GT_THREADS;
-    hipLaunchKernelGGL(bj::gate_terms_kernel, dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0,
-                       reinterpret_cast<hipStream_t>(stream), s->image_d + s->seg_offset[segment], cols, alphas, total,
-                       dst0, dst1);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "quotient gate terms");
+    hipLaunchKernelGGL(bj::gate_terms_kernel, dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, bj::stream_of(stream),
+                       s->image_d + s->seg_offset[segment], cols, alphas, total, dst0, dst1);
+    return bj::ok_or(hipGetLastError(), "quotient gate terms");
 }
 
 int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* vars, size_t vars_stride,
@@ -512,29 +508,12 @@ int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* v
         return bj::set_error(BJ_EINVAL, "bj_gate_set_satisfied_d: the row window is empty or ends past 2^32");
     if (s->need.alphas >= rows_cap)  // the key holds k in 32 bits, all ones being "none"
         return bj::set_error(BJ_EINVAL, "bj_gate_set_satisfied_d: the set has 2^32 terms or more");
-    const uint64_t end = row_begin + n_rows;
-    const uint64_t* p[3] = {vars, wits, consts};
-    const size_t stride[3] = {vars_stride, wits_stride, consts_stride};
-    const uint32_t have[3] = {n_vars, n_wits, n_consts};
-    static const char* const name[3] = {"variables", "witnesses", "constants"};
-    bj::Cols cols;
-    for (int k = 0; k < 3; k++) {
-        char msg[160];
-        if (s->need.cols[k] > have[k]) {
-            snprintf(msg, sizeof msg, "gate program: an operand reaches %s column %llu of %u", name[k],
-                     (unsigned long long)(s->need.cols[k] - 1), have[k]);
-            return bj::set_error(BJ_EINVAL, msg);
-        }
-        if (s->need.cols[k] && (!p[k] || stride[k] < end)) {
-            snprintf(msg, sizeof msg, "bj_gate_set_satisfied_d: %s are null or their stride is below row_begin + n_rows",
-                     name[k]);
-            return bj::set_error(BJ_EINVAL, msg);
-        }
-        // a kind no operand names is never read; point it at the record so no lane forms a null address
-        cols.p[k] = s->need.cols[k] ? p[k] : status_d;
-        cols.stride[k] = s->need.cols[k] ? stride[k] : 0;
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    bj::Cols cols;  // an unused kind points at the record
+    if (const int rc = bj::bind_columns(s->need, {vars, wits, consts}, {vars_stride, wits_stride, consts_stride},
+                                        {n_vars, n_wits, n_consts}, row_begin + n_rows, status_d,
+                                        "bj_gate_set_satisfied_d", "row_begin + n_rows", cols))
+        return rc;
+    hipStream_t st = bj::stream_of(stream);
     unsigned long long* status = reinterpret_cast<unsigned long long*>(status_d);
     const uint64_t* seg = s->image_d + s->seg_offset[segment];
     if (begin) hipLaunchKernelGGL(bj::gate_check_begin_kernel, dim3(1), dim3(bj::GC_WAVE), 0, st, status);
@@ -543,8 +522,7 @@ int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* v
                        row_begin, n_rows, status);
     hipLaunchKernelGGL(bj::gate_check_kernel<true>, dim3(1), dim3(bj::GC_WAVE), 0, st, seg, cols, row_begin, n_rows,
                        status);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "gate set satisfiability check");
+    return bj::ok_or(hipGetLastError(), "gate set satisfiability check");
 }
 
 }  // extern "C"

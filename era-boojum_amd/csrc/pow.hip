@@ -13,10 +13,9 @@
 // has left lies above the polled value.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
-#include "bj_internal.hpp"
 #include "capi_common.hpp"
 #include "pow_hash.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "stage_host.hpp"
 
 namespace bj {
 
@@ -166,16 +165,12 @@ int bj_pow_search_d(uint32_t hasher, const uint8_t* seed, size_t seed_len, uint3
     // the last nonce a window may hold is 2^64 - 2: 2^64 - 1 is BJ_POW_NO_RESULT (pow.rs:48, 61)
     if (n_nonces > BJ_POW_NO_RESULT - first_nonce)
         return bj::pow_einval("bj_pow_search_d", "first_nonce + n_nonces overflows");
-    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const hipStream_t st = bj::stream_of(stream);
     if (hasher == BJ_HASHER_BLAKE2S)
         bj::launch<bj::B2sPow>(seed, seed_len, pow_bits, first_nonce, n_nonces, result_d, st);
     else
         bj::launch<bj::KcPow>(seed, seed_len, pow_bits, first_nonce, n_nonces, result_d, st);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return BJ_OK;
-    char msg[160];
-    snprintf(msg, sizeof msg, "pow search: %s", hipGetErrorString(e));
-    return bj::set_error(BJ_EHIP, msg);
+    return bj::ok_or(hipGetLastError(), "pow search");
 }
 
 int bj_pow_run_h(uint32_t hasher, const uint8_t* seed, size_t seed_len, uint32_t pow_bits, uint64_t* nonce_out) {

@@ -18,9 +18,8 @@
 // carries every rank's records, and a second launch selects each query's owner's copy.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
-#include "bj_internal.hpp"
 #include "queries_sharded.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "stage_host.hpp"
 
 namespace bj {
 
@@ -323,11 +322,8 @@ int bj_oracle_queries_d(const bj_query_oracle_t* oracles, uint32_t n_oracles, co
         return bj::set_error(BJ_EINVAL, "bj_oracle_queries_d: out_words below n_queries * the oracles' record words");
     const uint32_t bx = n_queries < bj::QUERY_MAX_BLOCKS_X ? n_queries : bj::QUERY_MAX_BLOCKS_X;
     hipLaunchKernelGGL(bj::oracle_queries_kernel, dim3(bx, n_oracles), dim3(bj::QUERY_THREADS), 0,
-                       reinterpret_cast<hipStream_t>(stream), a, indices_d, n_queries, out_d, status_d);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return BJ_OK;
-    snprintf(msg, sizeof msg, "oracle queries: %s", hipGetErrorString(e));
-    return bj::set_error(BJ_EHIP, msg);
+                       bj::stream_of(stream), a, indices_d, n_queries, out_d, status_d);
+    return bj::ok_or(hipGetLastError(), "oracle queries");
 }
 
 }  // extern "C"

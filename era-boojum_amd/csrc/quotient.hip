@@ -32,12 +32,10 @@
 // Field arithmetic is exact, so any order of operations gives the reference's bits once the
 // outputs are canonical.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include "gl.hpp"
 #include "gl_asm.hpp"
 #include "ext2.hpp"
-#include "bj_internal.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "stage_host.hpp"
 
 namespace bj {
 
@@ -51,7 +49,6 @@ constexpr uint32_t QP_TILE = QP_ROWS * QP_THREADS;
 constexpr uint32_t QP_KCAP = 128;    // columns of one launch
 constexpr uint32_t QP_RCAP = 64;     // relations of one launch
 constexpr uint32_t Q_MAX = BJ_QUOTIENT_MAX_DEGREE;
-constexpr uint32_t LT_MAX_SRC = 16;
 constexpr uint32_t LT_THREADS = 256;
 static_assert(Q_MAX <= QP_KCAP, "a launch holds at least one whole chunk");
 
@@ -166,10 +163,7 @@ __global__ __launch_bounds__(QP_THREADS) void quotient_cp_kernel(
 }
 
 // ------------------------------------------------------------------ lookup term
-struct LtConsts {
-    const uint64_t* src[LT_MAX_SRC];
-    uint64_t g[2 * LT_MAX_SRC];  // canonical
-};
+struct LtConsts : LookupSources {};  // a type of this file's, so the kernel keeps its name
 
 // One point per thread: dst += alpha (E (beta + sum_t g_t src_t) - f), f = 1 when NULL.
 __global__ __launch_bounds__(LT_THREADS) void quotient_lookup_kernel(LtConsts k, uint32_t n_src, E2 beta,
@@ -226,14 +220,10 @@ hipError_t launch_quotient_cp(const uint64_t* vars, size_t vars_stride, const ui
     const size_t total = (size_t)1 << log_d;
     const uint32_t m = (uint32_t)(((uint64_t)n_cols + ((uint64_t)1 << log_q) - 1) >> log_q);
     QpConsts k;
-    uint64_t w = gl::domain_generator(log_d);
-    for (uint32_t b = 0; b < 32; b++) {
-        k.wpow[b] = gl::canon(w);
-        w = gl::mul(w, w);
-    }
+    fill_wpow(k.wpow, log_d);
     for (uint32_t i = 0; i < Q_MAX; i++) k.xn1[i] = 0;
     vanishing_on_cosets(log_n, log_q, k.xn1);
-    k.alpha[0] = {gl::canon(alphas[0]), gl::canon(alphas[1])};
+    k.alpha[0] = canon2(alphas[0], alphas[1]);
     // whole chunks per launch: at most QP_KCAP columns and QP_RCAP relations
     uint32_t per = QP_KCAP >> log_q;
     if (per > QP_RCAP) per = QP_RCAP;
@@ -244,7 +234,7 @@ hipError_t launch_quotient_cp(const uint64_t* vars, size_t vars_stride, const ui
         for (uint32_t c = 0; c < QP_KCAP; c++) k.k[c] = c0 + c < n_cols ? gl::canon(non_residues[c0 + c]) : 0;
         for (uint32_t r = 0; r < QP_RCAP; r++) {
             const uint32_t j = j0 + r;
-            k.alpha[1 + r] = j < j1 ? E2{gl::canon(alphas[2 * (j + 1)]), gl::canon(alphas[2 * (j + 1) + 1])} : E2{0, 0};
+            k.alpha[1 + r] = j < j1 ? canon2(alphas[2 * (j + 1)], alphas[2 * (j + 1) + 1]) : E2{0, 0};
         }
         hipLaunchKernelGGL(quotient_cp_kernel, dim3((unsigned)blocks), dim3(QP_THREADS), 0, st, vars, vars_stride,
                            sigmas, sigmas_stride, s2, s2_stride, n_cols, m, j0, j1, log_n, log_q, beta, gamma, k, dst0,
@@ -254,16 +244,9 @@ hipError_t launch_quotient_cp(const uint64_t* vars, size_t vars_stride, const ui
     return hipSuccess;
 }
 
-int hip_error(hipError_t e, const char* what) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-    return set_error(BJ_EHIP, msg);
-}
-
-// the checks every quotient entry point shares; NULL when the sizes are fine
-const char* bad_domain(uint32_t log_n, uint32_t log_q) {
-    if (log_n > 32 || log_q > 32 || log_n + log_q > 32)
-        return "log_n + log_q exceeds the 2-adicity (32) of the field";
+// the checks every device entry point of the quotient shares; NULL when the sizes are fine
+const char* bad_quotient_domain(uint32_t log_n, uint32_t log_q) {
+    if (const char* why = bad_domain(log_n, log_q)) return why;
     if (((uint64_t)1 << log_q) > Q_MAX) return "the quotient degree exceeds BJ_QUOTIENT_MAX_DEGREE";
     return nullptr;
 }
@@ -279,48 +262,41 @@ int bj_quotient_copy_permutation_d(const uint64_t* vars, size_t vars_stride, con
                                    uint32_t log_n, uint32_t log_q, const uint64_t* non_residues, uint64_t beta0,
                                    uint64_t beta1, uint64_t gamma0, uint64_t gamma1, const uint64_t* alphas,
                                    uint64_t* dst0, uint64_t* dst1, void* stream) {
-    if (const char* why = bj::bad_domain(log_n, log_q)) return bj::set_error(BJ_EINVAL, why);
+    if (const char* why = bj::bad_quotient_domain(log_n, log_q)) return bj::set_error(BJ_EINVAL, why);
     if (n_cols == 0) return bj::set_error(BJ_EINVAL, "bj_quotient_copy_permutation_d: n_cols must be positive");
     if (!vars || !sigmas || !stage2 || !non_residues || !alphas || !dst0 || !dst1)
         return bj::set_error(BJ_EINVAL, "bj_quotient_copy_permutation_d: null pointer");
     const size_t total = (size_t)1 << (log_n + log_q);
     if (vars_stride < total || sigmas_stride < total || stage2_stride < total)
         return bj::set_error(BJ_EINVAL, "bj_quotient_copy_permutation_d: a column stride is below 2^(log_n + log_q)");
-    const hipError_t e = bj::launch_quotient_cp(
-        vars, vars_stride, sigmas, sigmas_stride, stage2, stage2_stride, n_cols, log_n, log_q, non_residues,
-        bj::ext2::E2{gl::canon(beta0), gl::canon(beta1)}, bj::ext2::E2{gl::canon(gamma0), gl::canon(gamma1)}, alphas,
-        dst0, dst1, reinterpret_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "quotient copy permutation");
+    const hipError_t e = bj::launch_quotient_cp(vars, vars_stride, sigmas, sigmas_stride, stage2, stage2_stride, n_cols,
+                                                log_n, log_q, non_residues, bj::ext2::canon2(beta0, beta1),
+                                                bj::ext2::canon2(gamma0, gamma1), alphas, dst0, dst1,
+                                                bj::stream_of(stream));
+    return bj::ok_or(e, "quotient copy permutation");
 }
 
 int bj_quotient_lookup_term_d(const uint64_t* const* srcs, uint32_t n_src, const uint64_t* g, uint64_t beta0,
                               uint64_t beta1, const uint64_t* e_c0, const uint64_t* e_c1, const uint64_t* f,
                               uint64_t alpha0, uint64_t alpha1, uint32_t log_n, uint32_t log_q, uint64_t* dst0,
                               uint64_t* dst1, void* stream) {
-    if (const char* why = bj::bad_domain(log_n, log_q)) return bj::set_error(BJ_EINVAL, why);
-    if (n_src == 0 || n_src > bj::LT_MAX_SRC)
+    if (const char* why = bj::bad_quotient_domain(log_n, log_q)) return bj::set_error(BJ_EINVAL, why);
+    if (n_src == 0 || n_src > bj::LOOKUP_MAX_SRC)
         return bj::set_error(BJ_EINVAL, "bj_quotient_lookup_term_d: n_src must be 1..16");
     if (!srcs || !g || !e_c0 || !e_c1 || !dst0 || !dst1)
         return bj::set_error(BJ_EINVAL, "bj_quotient_lookup_term_d: null pointer");
     bj::LtConsts k;
-    for (uint32_t t = 0; t < bj::LT_MAX_SRC; t++) {
-        k.src[t] = t < n_src ? srcs[t] : nullptr;
-        k.g[2 * t] = t < n_src ? gl::canon(g[2 * t]) : 0;
-        k.g[2 * t + 1] = t < n_src ? gl::canon(g[2 * t + 1]) : 0;
-        if (t < n_src && !srcs[t]) return bj::set_error(BJ_EINVAL, "bj_quotient_lookup_term_d: null source column");
-    }
+    if (!bj::fill_lookup_sources(k, srcs, n_src, g))
+        return bj::set_error(BJ_EINVAL, "bj_quotient_lookup_term_d: null source column");
     const size_t total = (size_t)1 << (log_n + log_q);
     hipLaunchKernelGGL(bj::quotient_lookup_kernel, dim3((unsigned)((total + bj::LT_THREADS - 1) / bj::LT_THREADS)),
-                       dim3(bj::LT_THREADS), 0, reinterpret_cast<hipStream_t>(stream), k, n_src,
-                       bj::ext2::E2{gl::canon(beta0), gl::canon(beta1)}, e_c0, e_c1, f,
-                       bj::ext2::E2{gl::canon(alpha0), gl::canon(alpha1)}, total, dst0, dst1);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "quotient lookup term");
+                       dim3(bj::LT_THREADS), 0, bj::stream_of(stream), k, n_src, bj::ext2::canon2(beta0, beta1), e_c0,
+                       e_c1, f, bj::ext2::canon2(alpha0, alpha1), total, dst0, dst1);
+    return bj::ok_or(hipGetLastError(), "quotient lookup term");
 }
 
 int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out) {
-    if (log_n > 32 || log_q > 32 || log_n + log_q > 32)
-        return bj::set_error(BJ_EINVAL, "log_n + log_q exceeds the 2-adicity (32) of the field");
+    if (const char* why = bj::bad_domain(log_n, log_q)) return bj::set_error(BJ_EINVAL, why);
     if (!out) return bj::set_error(BJ_EINVAL, "bj_vanishing_inverses_h: null out");
     // 7 generates the whole multiplicative group and nq < p - 1, so 7^n w_q^k is never 1
     const uint64_t wq = gl::domain_generator(log_q);
@@ -333,16 +309,15 @@ int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out) {
 }
 
 int bj_quotient_divide_vanishing_d(uint64_t* dst0, uint64_t* dst1, uint32_t log_n, uint32_t log_q, void* stream) {
-    if (const char* why = bj::bad_domain(log_n, log_q)) return bj::set_error(BJ_EINVAL, why);
+    if (const char* why = bj::bad_quotient_domain(log_n, log_q)) return bj::set_error(BJ_EINVAL, why);
     if (!dst0 || !dst1) return bj::set_error(BJ_EINVAL, "bj_quotient_divide_vanishing_d: null pointer");
     bj::DvConsts k;
     for (uint32_t i = 0; i < bj::Q_MAX; i++) k.inv[i] = 0;
     if (const int rc = bj_vanishing_inverses_h(log_n, log_q, k.inv)) return rc;
     const size_t total = (size_t)1 << (log_n + log_q);
     hipLaunchKernelGGL(bj::quotient_divide_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), k, log_n, total, dst0, dst1);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "quotient divide by vanishing");
+                       bj::stream_of(stream), k, log_n, total, dst0, dst1);
+    return bj::ok_or(hipGetLastError(), "quotient divide by vanishing");
 }
 
 }  // extern "C"

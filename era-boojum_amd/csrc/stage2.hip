@@ -29,13 +29,11 @@
 // Field arithmetic is exact, so any order of operations gives the reference's bits once the
 // outputs are canonical.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <vector>
 #include "gl.hpp"
 #include "gl_asm.hpp"
 #include "ext2.hpp"
-#include "bj_internal.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "stage_host.hpp"
 
 namespace bj {
 
@@ -47,7 +45,6 @@ constexpr uint32_t CP_TILE = 128;   // rows of one block of the rational pass: t
 constexpr uint32_t CP_KCAP = 256;   // columns of one rational launch
 constexpr uint32_t CP_MP = 16;      // chunks that share one inversion, at most (16 bytes of LDS per row each)
 constexpr uint32_t TOTALS_THREADS = 256;
-constexpr uint32_t LK_MAX_SRC = 16;
 constexpr uint32_t LK_ROWS = 4;     // rows of a thread, sharing one inversion
 constexpr uint32_t LK_THREADS = 256;
 constexpr uint32_t LK_TILE = LK_ROWS * LK_THREADS;
@@ -248,10 +245,7 @@ __global__ __launch_bounds__(256) void cp_apply_kernel(uint64_t* __restrict__ ou
 }
 
 // ------------------------------------------------------------------ lookup encodings
-struct LkConsts {
-    const uint64_t* src[LK_MAX_SRC];
-    uint64_t g[2 * LK_MAX_SRC];  // canonical
-};
+struct LkConsts : LookupSources {};  // a type of this file's, so the kernel keeps its name
 
 // A thread owns rows base + r * LK_THREADS, r < LK_ROWS, so every load and store is contiguous over
 // the wave; the rows' Ext2 inverses share one base inversion of the product of their norms.  A
@@ -321,11 +315,7 @@ hipError_t launch_copy_permutation(const uint64_t* vars, size_t vars_stride, con
     const uint32_t n_groups = (m + CP_MP - 1) / CP_MP;
     const uint32_t group = (m + n_groups - 1) / n_groups;
     CpConsts k;
-    uint64_t w = gl::domain_generator(log_n);
-    for (uint32_t b = 0; b < 32; b++) {
-        k.wpow[b] = gl::canon(w);
-        w = gl::mul(w, w);
-    }
+    fill_wpow(k.wpow, log_n);
     for (uint32_t c0 = 0; c0 < n_cols; c0 += CP_KCAP) {
         const uint32_t c1 = n_cols - c0 < CP_KCAP ? n_cols : c0 + CP_KCAP;
         for (uint32_t c = 0; c < CP_KCAP; c++) k.k[c] = c0 + c < c1 ? gl::canon(non_residues[c0 + c]) : 0;
@@ -343,12 +333,6 @@ hipError_t launch_copy_permutation(const uint64_t* vars, size_t vars_stride, con
     return hipGetLastError();
 }
 
-int hip_error(hipError_t e, const char* what) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-    return set_error(BJ_EHIP, msg);
-}
-
 }  // namespace
 
 }  // namespace bj
@@ -359,7 +343,7 @@ int bj_copy_permutation_d(const uint64_t* vars, size_t vars_stride, const uint64
                           uint32_t n_cols, uint32_t log_n, const uint64_t* non_residues, uint64_t beta0, uint64_t beta1,
                           uint64_t gamma0, uint64_t gamma1, uint32_t chunk, uint64_t* out, size_t out_stride,
                           uint64_t* status_d, void* stream) {
-    if (log_n > 32) return bj::set_error(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
+    if (const char* why = bj::bad_log_n(log_n)) return bj::set_error(BJ_EINVAL, why);
     if (n_cols == 0) return bj::set_error(BJ_EINVAL, "bj_copy_permutation_d: n_cols must be positive");
     if (chunk == 0 || (chunk & (chunk - 1)))
         return bj::set_error(BJ_EINVAL, "bj_copy_permutation_d: chunk must be a power of two");
@@ -369,42 +353,38 @@ int bj_copy_permutation_d(const uint64_t* vars, size_t vars_stride, const uint64
     if (vars_stride < n || sigmas_stride < n || out_stride < n)
         return bj::set_error(BJ_EINVAL, "bj_copy_permutation_d: a column stride is below 2^log_n");
     const uint32_t log_q = (uint32_t)__builtin_ctz(chunk);
-    const hipError_t e = bj::launch_copy_permutation(
-        vars, vars_stride, sigmas, sigmas_stride, n_cols, log_n, non_residues,
-        bj::ext2::E2{gl::canon(beta0), gl::canon(beta1)}, bj::ext2::E2{gl::canon(gamma0), gl::canon(gamma1)}, log_q, out,
-        out_stride, status_d, reinterpret_cast<hipStream_t>(stream));
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "copy permutation");
+    const hipError_t e = bj::launch_copy_permutation(vars, vars_stride, sigmas, sigmas_stride, n_cols, log_n,
+                                                     non_residues, bj::ext2::canon2(beta0, beta1),
+                                                     bj::ext2::canon2(gamma0, gamma1), log_q, out, out_stride, status_d,
+                                                     bj::stream_of(stream));
+    return bj::ok_or(e, "copy permutation");
 }
 
 int bj_lookup_encoding_d(const uint64_t* const* srcs, uint32_t n_src, const uint64_t* g, uint64_t beta0, uint64_t beta1,
                          const uint64_t* f, uint32_t log_n, uint64_t* out_c0, uint64_t* out_c1, uint64_t* status_d,
                          void* stream) {
-    if (log_n > 32) return bj::set_error(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
-    if (n_src == 0 || n_src > bj::LK_MAX_SRC)
+    if (const char* why = bj::bad_log_n(log_n)) return bj::set_error(BJ_EINVAL, why);
+    if (n_src == 0 || n_src > bj::LOOKUP_MAX_SRC)
         return bj::set_error(BJ_EINVAL, "bj_lookup_encoding_d: n_src must be 1..16");
     if (!srcs || !g || !out_c0 || !out_c1 || !status_d)
         return bj::set_error(BJ_EINVAL, "bj_lookup_encoding_d: null pointer");
     bj::LkConsts k;
-    for (uint32_t t = 0; t < bj::LK_MAX_SRC; t++) {
-        k.src[t] = t < n_src ? srcs[t] : nullptr;
-        k.g[2 * t] = t < n_src ? gl::canon(g[2 * t]) : 0;
-        k.g[2 * t + 1] = t < n_src ? gl::canon(g[2 * t + 1]) : 0;
-        if (t < n_src && !srcs[t]) return bj::set_error(BJ_EINVAL, "bj_lookup_encoding_d: null source column");
-    }
+    if (!bj::fill_lookup_sources(k, srcs, n_src, g))
+        return bj::set_error(BJ_EINVAL, "bj_lookup_encoding_d: null source column");
     const size_t n = (size_t)1 << log_n;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = bj::stream_of(stream);
     hipError_t e = hipMemsetAsync(status_d, 0, 4 * sizeof(uint64_t), st);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(bj::lookup_encoding_kernel, dim3((unsigned)((n + bj::LK_TILE - 1) / bj::LK_TILE)),
-                           dim3(bj::LK_THREADS), 0, st, k, n_src, bj::ext2::E2{gl::canon(beta0), gl::canon(beta1)}, f, n,
-                           out_c0, out_c1, reinterpret_cast<unsigned long long*>(status_d));
+                           dim3(bj::LK_THREADS), 0, st, k, n_src, bj::ext2::canon2(beta0, beta1), f, n, out_c0, out_c1,
+                           reinterpret_cast<unsigned long long*>(status_d));
         e = hipGetLastError();
     }
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "lookup encoding");
+    return bj::ok_or(e, "lookup encoding");
 }
 
 int bj_non_residues_h(uint32_t num, uint32_t log_n, uint64_t* out) {
-    if (log_n > 32) return bj::set_error(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
+    if (const char* why = bj::bad_log_n(log_n)) return bj::set_error(BJ_EINVAL, why);
     if (num == 0 || !out) return bj::set_error(BJ_EINVAL, "bj_non_residues_h: num must be positive and out non-null");
     // x^n by log_n squarings
     auto pow_n = [log_n](uint64_t x) {

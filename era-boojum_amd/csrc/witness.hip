@@ -28,12 +28,10 @@
 // call compares num_values with it on the host, so there is no bound check per lane and no status
 // record.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <new>
 #include <vector>
 #include "gl.hpp"
-#include "bj_internal.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "stage_host.hpp"
 
 // the A/B switches of DESIGN 4.14, compile time only
 #ifndef BJ_WIT_DEAL_BY_XCD
@@ -136,12 +134,6 @@ __global__ __launch_bounds__(WIT_THREADS) void permutation_polys_kernel(const ui
     __builtin_nontemporal_store(x, out + (size_t)col * out_stride + row);
 }
 
-int hip_error(hipError_t e, const char* what) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-    return set_error(BJ_EHIP, msg);
-}
-
 const CopyHint* live(const void* hint) {
     const CopyHint* h = static_cast<const CopyHint*>(hint);
     return h && h->magic == HINT_MAGIC ? h : nullptr;
@@ -216,7 +208,7 @@ int bj_copy_hint_release(void* hint) {
     h->magic = 0;
     const hipError_t e = hipFree(h->cells_d);
     delete h;
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "copy hint release");
+    return bj::ok_or(e, "copy hint release");
 }
 
 int bj_copy_hint_info(const void* hint, uint32_t* n_cols, uint64_t* n_rows, uint64_t* max_index,
@@ -248,10 +240,9 @@ int bj_materialize_columns_d(const void* hint, const uint64_t* all_values, uint6
     if (padded * col_tiles > 0x7fffffffull)
         return bj::set_error(BJ_EINVAL, "bj_materialize_columns_d: more workgroups than one grid holds");
     hipLaunchKernelGGL(bj::materialize_kernel, dim3((unsigned)(padded * col_tiles)), dim3(bj::WIT_THREADS), 0,
-                       reinterpret_cast<hipStream_t>(stream), h->cells_d, h->n_cols, (size_t)h->n_rows,
-                       (uint32_t)row_blocks, (uint32_t)col_tiles, all_values, out, out_stride);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "materialize columns");
+                       bj::stream_of(stream), h->cells_d, h->n_cols, (size_t)h->n_rows, (uint32_t)row_blocks,
+                       (uint32_t)col_tiles, all_values, out, out_stride);
+    return bj::ok_or(hipGetLastError(), "materialize columns");
 }
 
 int bj_materialize_multiplicities_d(const uint32_t* mult_u32, uint64_t len, uint64_t* out, uint64_t n_rows,
@@ -263,9 +254,8 @@ int bj_materialize_multiplicities_d(const uint32_t* mult_u32, uint64_t len, uint
     if (blocks > 0x7fffffffull)
         return bj::set_error(BJ_EINVAL, "bj_materialize_multiplicities_d: more workgroups than one grid holds");
     hipLaunchKernelGGL(bj::multiplicities_kernel, dim3((unsigned)blocks), dim3(bj::WIT_THREADS), 0,
-                       reinterpret_cast<hipStream_t>(stream), mult_u32, (size_t)len, out, (size_t)n_rows);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "materialize multiplicities");
+                       bj::stream_of(stream), mult_u32, (size_t)len, out, (size_t)n_rows);
+    return bj::ok_or(hipGetLastError(), "materialize multiplicities");
 }
 
 int bj_permutation_polys_d(const uint32_t* prev, uint32_t n_cols, uint64_t n_rows, const uint64_t* non_residues,
@@ -278,25 +268,24 @@ int bj_permutation_polys_d(const uint32_t* prev, uint32_t n_cols, uint64_t n_row
     if (n_cols == 0 || n_cols > 65535 || (uint64_t)n_cols * n > ((uint64_t)1 << 32))
         return bj::set_error(BJ_EINVAL, "bj_permutation_polys_d: n_cols outside 1..65535 or more than 2^32 cells");
     if (out_stride < n) return bj::set_error(BJ_EINVAL, "bj_permutation_polys_d: out_stride is below n_rows");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = bj::stream_of(stream);
     const size_t half = log_n ? (size_t)(n >> 1) : 0;
     std::vector<uint64_t> k(n_cols);
     for (uint32_t c = 0; c < n_cols; c++) k[c] = gl::canon(non_residues[c]);
-    uint64_t* tab = nullptr;
-    hipError_t e = bj::pool_alloc(reinterpret_cast<void**>(&tab), (n_cols + half) * sizeof(uint64_t), st);
+    bj::Scratch tab(st);
+    hipError_t e = tab.alloc(n_cols + half);
     if (e != hipSuccess) return bj::hip_error(e, "permutation polys table");
     // k is pageable host memory: the copy has left it when the call returns
-    e = hipMemcpyAsync(tab, k.data(), n_cols * sizeof(uint64_t), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(tab.p, k.data(), n_cols * sizeof(uint64_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && log_n) e = bj::launch_twiddles_natural(tab + n_cols, log_n, false, st);
+    if (e == hipSuccess && log_n) e = bj::launch_twiddles_natural(tab.p + n_cols, log_n, false, st);
     if (e == hipSuccess) {
         const uint64_t blocks = (n + bj::WIT_THREADS - 1) / bj::WIT_THREADS;
         hipLaunchKernelGGL(bj::permutation_polys_kernel, dim3((unsigned)blocks, n_cols), dim3(bj::WIT_THREADS), 0, st,
-                           prev, n_cols, log_n, tab, out, out_stride);
+                           prev, n_cols, log_n, tab.p, out, out_stride);
         e = hipGetLastError();
     }
-    (void)hipFreeAsync(tab, st);
-    return e == hipSuccess ? BJ_OK : bj::hip_error(e, "permutation polys");
+    return bj::ok_or(e, "permutation polys");
 }
 
 }  // extern "C"
