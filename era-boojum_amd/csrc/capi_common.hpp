@@ -1,32 +1,18 @@
-// What the C ABI files (capi.hip, capi_tree.hip) share, host only: error returns, the stream
-// cast, and the stream and buffers of the host-pointer (*_h) entry points.
+// What the C ABI files (capi.hip, capi_tree.hip) add to host.hpp: the stream and buffers of the
+// host-pointer (*_h) entry points.  Host only.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <map>
-#include <string>
 
-#include "../../include/boojum_mi355x.h"
-#include "bj_internal.hpp"
+#include "host.hpp"
 
 namespace bj {
 namespace capi {
 
-// the message goes to the calling thread's bj_last_error() string (bj::set_error, capi.hip)
-inline int fail(int code, const std::string& msg) { return bj::set_error(code, msg.c_str()); }
-
-inline int hip_fail(hipError_t e, const char* what) {
-    return fail(BJ_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(expr, what)                       \
-    do {                                          \
-        hipError_t _e = (expr);                   \
-        if (_e != hipSuccess) return hip_fail(_e, what); \
-    } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
+// the shared names (host.hpp) that capi.hip and capi_tree.hip use through this namespace
+using bj::fail;
+using bj::hip_fail;
+using bj::is_pow2;
+using bj::S;
 
 // The *_h entry points run on a stream of their own per calling thread and device (created
 // once; stream creation costs milliseconds on ROCm), with stream-ordered device buffers and
@@ -46,14 +32,15 @@ inline int seam_stream(hipStream_t* out) {
     return BJ_OK;
 }
 
-// Stream-ordered device buffer RAII for the *_h entry points.
+// One stream-ordered device buffer of the *_h entry points, sized in bytes.
+namespace {
 struct DBuf {
     uint64_t* p = nullptr;
-    hipStream_t st = nullptr;
-    explicit DBuf(hipStream_t s) : st(s) {}
-    hipError_t alloc(size_t bytes) { return bj::pool_alloc((void**)&p, bytes, st); }
-    ~DBuf() { if (p) (void)hipFreeAsync(p, st); }
+    Workspace ws;
+    explicit DBuf(hipStream_t s) : ws(s) {}
+    hipError_t alloc(size_t bytes) { return ws.alloc_bytes(&p, bytes); }
 };
+}  // namespace
 
 #define SEAM_BEGIN            \
     hipStream_t st;           \

@@ -53,8 +53,7 @@ int tree_nodes(int hasher, const uint64_t* leaves, size_t n_leaves, uint32_t cap
 int tree_leaves_chunked(int hasher, const uint64_t* src, uint32_t n_cols, size_t col_stride, size_t n_leaves,
                         uint32_t elems_per_leaf, uint64_t* out, hipStream_t st) {
     if (!is_pow2(elems_per_leaf)) return fail(BJ_EINVAL, "elements_to_take_per_leaf must be a power of two");
-    uint32_t log_e = 0;
-    while ((1u << log_e) < elems_per_leaf) log_e++;
+    const uint32_t log_e = log2u(elems_per_leaf);
     if ((uint64_t)n_cols << log_e > 0xFFFFFFFFull) return fail(BJ_EINVAL, "leaf too long");
     HIP_TRY(tree_ops(hasher)->leaves_chunked(src, col_stride, n_cols, log_e, n_leaves, out, st), "leaves");
     return BJ_OK;

@@ -275,12 +275,13 @@ hipError_t launch_weights(uint32_t log_n, uint64_t coset, uint64_t at0, uint64_t
     const uint64_t k = gl::inv(gl::mul(cn, gl::canon((uint64_t)n)));
     const uint64_t c0 = gl::canon(gl::mul(gl::sub(an.c0, cn), k)), c1 = gl::canon(gl::mul(an.c1, k));
     const uint64_t s7 = gl::canon(times7(gl::mul(at1, at1)));
-    Scratch tab(st);
-    if (hipError_t e = tab.alloc(POW_TAB_WORDS)) return e;
-    if (hipError_t e = launch_pow_table(tab.p, gl::domain_generator(log_n), coset, st)) return e;
+    Workspace ws(st);
+    uint64_t* tab = nullptr;
+    if (hipError_t e = ws.alloc(&tab, POW_TAB_WORDS)) return e;
+    if (hipError_t e = launch_pow_table(tab, gl::domain_generator(log_n), coset, st)) return e;
     size_t blocks = (n + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(weights_kernel, dim3((unsigned)blocks), dim3(256), 0, st, tab.p, log_n, c0, c1, gl::canon(at0),
+    hipLaunchKernelGGL(weights_kernel, dim3((unsigned)blocks), dim3(256), 0, st, tab, log_n, c0, c1, gl::canon(at0),
                        gl::canon(at1), s7, w0, w1);
     return hipGetLastError();
 }
@@ -296,12 +297,13 @@ hipError_t launch_evaluate_at(const uint64_t* cols, uint32_t n_cols, size_t col_
     size_t rpb = n / max_ranges;
     if (rpb < EVAL_MIN_ROWS) rpb = EVAL_MIN_ROWS;
     const size_t ranges = (n + rpb - 1) / rpb;
-    Scratch partial(st);
-    if (hipError_t e = partial.alloc(ranges * n_cols * 2)) return e;
+    Workspace ws(st);
+    uint64_t* partial = nullptr;
+    if (hipError_t e = ws.alloc(&partial, ranges * n_cols * 2)) return e;
     hipLaunchKernelGGL(evaluate_partial_kernel, dim3(tiles, (unsigned)ranges), dim3(256), 0, st, cols, n_cols,
-                       col_stride, n, rpb, w0, w1, partial.p);
+                       col_stride, n, rpb, w0, w1, partial);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(evaluate_finish_kernel, dim3(n_cols), dim3(256), 0, st, partial.p, n_cols, (uint32_t)ranges, out);
+    hipLaunchKernelGGL(evaluate_finish_kernel, dim3(n_cols), dim3(256), 0, st, partial, n_cols, (uint32_t)ranges, out);
     return hipGetLastError();
 }
 
@@ -312,9 +314,10 @@ hipError_t launch_deep_quotient(const uint64_t* cols, uint32_t n_cols, size_t co
     at0 = gl::canon(at0);
     at1 = gl::canon(at1);
     const uint64_t s7 = gl::canon(times7(gl::mul(at1, at1)));
-    Scratch tab(st);
-    if (hipError_t e = tab.alloc(POW_TAB_WORDS)) return e;
-    if (hipError_t e = launch_pow_table(tab.p, gl::domain_generator(log_domain), gl::GENERATOR, st)) return e;
+    Workspace ws(st);
+    uint64_t* tab = nullptr;
+    if (hipError_t e = ws.alloc(&tab, POW_TAB_WORDS)) return e;
+    if (hipError_t e = launch_pow_table(tab, gl::domain_generator(log_domain), gl::GENERATOR, st)) return e;
     const uint32_t pair_bits = log_domain ? log_domain - 1 : 0;
     const size_t n_pairs = ((row0 + n_rows + 1) >> 1) - (row0 >> 1);
     const size_t blocks = (n_pairs + 255) / 256;  // at most 2^23
@@ -323,7 +326,7 @@ hipError_t launch_deep_quotient(const uint64_t* cols, uint32_t n_cols, size_t co
     const bool v16 = (row0 & 1) == 0 && (n_rows & 1) == 0 && align % 16 == 0 && (n_cols <= 1 || (col_stride & 1) == 0);
     auto kernel = v16 ? deep_quotient_kernel<true> : deep_quotient_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, cols, n_cols, col_stride, gammas,
-                       gl::canon(k0), gl::canon(k1), at0, at1, s7, tab.p, pair_bits, row0, n_rows, n_pairs, dst0, dst1,
+                       gl::canon(k0), gl::canon(k1), at0, at1, s7, tab, pair_bits, row0, n_rows, n_pairs, dst0, dst1,
                        accumulate);
     return hipGetLastError();
 }
@@ -339,7 +342,7 @@ int bj_barycentric_weights_d(uint32_t log_n, uint64_t coset, uint64_t at0, uint6
     if (const char* why = bj::bad_log_n(log_n)) return bj::set_error(BJ_EINVAL, why);
     if (!w0 || !w1) return bj::set_error(BJ_EINVAL, "bj_barycentric_weights_d: null output");
     if (gl::canon(coset) == 0) return bj::set_error(BJ_EINVAL, "bj_barycentric_weights_d: coset must be non-zero");
-    const hipError_t e = bj::launch_weights(log_n, coset, at0, at1, w0, w1, bj::stream_of(stream));
+    const hipError_t e = bj::launch_weights(log_n, coset, at0, at1, w0, w1, bj::S(stream));
     return bj::ok_or(e, "barycentric weights");
 }
 
@@ -349,7 +352,7 @@ int bj_evaluate_at_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride, u
     if (n_cols == 0) return BJ_OK;
     if (!cols || !w0 || !w1 || !out) return bj::set_error(BJ_EINVAL, "bj_evaluate_at_d: null pointer");
     if (col_stride < ((size_t)1 << log_n)) return bj::set_error(BJ_EINVAL, "bj_evaluate_at_d: col_stride < 2^log_n");
-    const hipError_t e = bj::launch_evaluate_at(cols, n_cols, col_stride, log_n, w0, w1, out, bj::stream_of(stream));
+    const hipError_t e = bj::launch_evaluate_at(cols, n_cols, col_stride, log_n, w0, w1, out, bj::S(stream));
     return bj::ok_or(e, "evaluate at");
 }
 
@@ -365,7 +368,7 @@ int bj_deep_quotient_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride,
     if (n_cols && (!cols || !gammas)) return bj::set_error(BJ_EINVAL, "bj_deep_quotient_d: null cols or gammas");
     if (n_cols && col_stride < n_rows) return bj::set_error(BJ_EINVAL, "bj_deep_quotient_d: col_stride < n_rows");
     const hipError_t e = bj::launch_deep_quotient(cols, n_cols, col_stride, gammas, k0, k1, at0, at1, log_domain, row0,
-                                                  n_rows, dst0, dst1, accumulate, bj::stream_of(stream));
+                                                  n_rows, dst0, dst1, accumulate, bj::S(stream));
     return bj::ok_or(e, "deep quotient");
 }
 

@@ -211,7 +211,7 @@ int bj_fri_fold_multi_d(const uint64_t* c0, const uint64_t* c1, size_t n_src, co
     if (!c0 || !c1 || !roots || !dst_c0 || !dst_c1) return bj::set_error(BJ_EINVAL, "bj_fri_fold_multi_d: null pointer");
     if (((uintptr_t)c0 | (uintptr_t)c1 | (uintptr_t)roots | (uintptr_t)dst_c0 | (uintptr_t)dst_c1) % 8)
         return bj::set_error(BJ_EINVAL, "bj_fri_fold_multi_d: a pointer is not 8-byte aligned");
-    const hipStream_t st = bj::stream_of(stream);
+    const hipStream_t st = bj::S(stream);
     const size_t n_out = n_src >> log_fold;
     hipError_t e;
     if (log_fold == 1) {
@@ -224,7 +224,7 @@ int bj_fri_fold_multi_d(const uint64_t* c0, const uint64_t* c1, size_t n_src, co
     if (e == hipSuccess) return BJ_OK;
     char what[32];
     snprintf(what, sizeof what, "fri fold by 2^%u", log_fold);
-    return bj::hip_error(e, what);
+    return bj::hip_fail(e, what);
 }
 
 }  // extern "C"

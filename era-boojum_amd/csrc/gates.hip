@@ -454,7 +454,7 @@ int bj_gate_set_upload_d(const uint64_t* image, size_t words, void** set) {
     }
     if (e != hipSuccess) {
         delete s;
-        return bj::hip_error(e, "gate set upload");
+        return bj::hip_fail(e, "gate set upload");
     }
     *set = s;
     return BJ_OK;
@@ -488,7 +488,7 @@ int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* 
         return rc;
     if (s->need.alphas > n_alphas) return bj::set_error(BJ_EINVAL, "gate program: fewer challenges than terms");
     const size_t blocks = (total + bj::GT_THREADS - 1) / bj::GT_THREADS;
-    hipLaunchKernelGGL(bj::gate_terms_kernel, dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, bj::stream_of(stream),
+    hipLaunchKernelGGL(bj::gate_terms_kernel, dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, bj::S(stream),
                        s->image_d + s->seg_offset[segment], cols, alphas, total, dst0, dst1);
     return bj::ok_or(hipGetLastError(), "quotient gate terms");
 }
@@ -513,7 +513,7 @@ int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* v
                                         {n_vars, n_wits, n_consts}, row_begin + n_rows, status_d,
                                         "bj_gate_set_satisfied_d", "row_begin + n_rows", cols))
         return rc;
-    hipStream_t st = bj::stream_of(stream);
+    hipStream_t st = bj::S(stream);
     unsigned long long* status = reinterpret_cast<unsigned long long*>(status_d);
     const uint64_t* seg = s->image_d + s->seg_offset[segment];
     if (begin) hipLaunchKernelGGL(bj::gate_check_begin_kernel, dim3(1), dim3(bj::GC_WAVE), 0, st, status);

@@ -27,19 +27,11 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/boojum_mi355x.h"
-#include "bj_internal.hpp"
+#include "host.hpp"
+
+using namespace bj;
 
 namespace {
-
-int err(int code, const std::string& msg) { return bj::set_error(code, msg.c_str()); }
-int hip_err(hipError_t e, const char* what) { return err(BJ_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-#define HIP_CHECK(expr, what)                         \
-    do {                                              \
-        hipError_t e_ = (expr);                       \
-        if (e_ != hipSuccess) return hip_err(e_, what); \
-    } while (0)
 
 // Persistent host threads for parallel memcpy (never destroyed: they sleep between calls).
 class CopyPool {
@@ -137,12 +129,12 @@ StagingPool& staging_pool() {
 
 int make_staging(Staging* sg) {
     for (int i = 0; i < RING; i++) {
-        HIP_CHECK(hipHostMalloc((void**)&sg->out[i], SLOT, hipHostMallocDefault), "hipHostMalloc");
-        HIP_CHECK(hipEventCreateWithFlags(&sg->out_ev[i], hipEventDisableTiming), "hipEventCreate");
+        HIP_TRY(hipHostMalloc((void**)&sg->out[i], SLOT, hipHostMallocDefault), "hipHostMalloc");
+        HIP_TRY(hipEventCreateWithFlags(&sg->out_ev[i], hipEventDisableTiming), "hipEventCreate");
     }
-    HIP_CHECK(hipStreamCreateWithFlags(&sg->s_in, hipStreamNonBlocking), "hipStreamCreate");
-    HIP_CHECK(hipStreamCreateWithFlags(&sg->s_cmp, hipStreamNonBlocking), "hipStreamCreate");
-    HIP_CHECK(hipStreamCreateWithFlags(&sg->s_out, hipStreamNonBlocking), "hipStreamCreate");
+    HIP_TRY(hipStreamCreateWithFlags(&sg->s_in, hipStreamNonBlocking), "hipStreamCreate");
+    HIP_TRY(hipStreamCreateWithFlags(&sg->s_cmp, hipStreamNonBlocking), "hipStreamCreate");
+    HIP_TRY(hipStreamCreateWithFlags(&sg->s_out, hipStreamNonBlocking), "hipStreamCreate");
     return BJ_OK;
 }
 
@@ -151,7 +143,7 @@ struct StagingLease {
     Staging* sg = nullptr;
     int dev = 0;
     int acquire() {
-        HIP_CHECK(hipGetDevice(&dev), "hipGetDevice");
+        HIP_TRY(hipGetDevice(&dev), "hipGetDevice");
         StagingPool& p = staging_pool();
         std::unique_lock<std::mutex> lk(p.mu);
         for (;;) {
@@ -275,15 +267,15 @@ hipError_t d2h(Staging& sg, void* host, const void* dev, size_t bytes, bool pinn
 extern "C" int bj_lde_commit_h(const uint64_t* trace_h, uint32_t n_cols, uint32_t log_n, uint32_t log_lde,
                                uint32_t log_commit_cosets, uint32_t cap_size, uint64_t* lde_h, uint64_t* leaves_h,
                                uint64_t* nodes_h, uint64_t* cap_h) {
-    if (log_n + log_lde > 32) return err(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
+    if (log_n + log_lde > 32) return fail(BJ_EINVAL, "log_n exceeds the 2-adicity (32) of the field");
     if (log_commit_cosets > log_lde)
-        return err(BJ_EINVAL, "committed cosets exceed the lde degree (prover.rs:313, lde.rs:298-308)");
+        return fail(BJ_EINVAL, "committed cosets exceed the lde degree (prover.rs:313, lde.rs:298-308)");
     // nd: LDE length per column (all D cosets); nl: leaves, the first k cosets (subset_for_degree)
     const size_t n = (size_t)1 << log_n, nd = n << log_lde, nl = n << log_commit_cosets;
     if (!cap_size || (cap_size & (cap_size - 1)) || nl <= cap_size)
-        return err(BJ_EINVAL, "need power-of-two cap_size < n * k");
-    if (log_lde == 0) return err(BJ_EINVAL, "lde degree must be > 1 (utils.rs:283)");
-    if (n_cols && !trace_h) return err(BJ_EINVAL, "null trace");
+        return fail(BJ_EINVAL, "need power-of-two cap_size < n * k");
+    if (log_lde == 0) return fail(BJ_EINVAL, "lde degree must be > 1 (utils.rs:283)");
+    if (n_cols && !trace_h) return fail(BJ_EINVAL, "null trace");
     // chunk k covers columns [c_first[k], c_first[k + 1]): 8, 8, 16, then 32 at a time (every
     // chunk but the last a multiple of the sponge rate), so the first LDE columns start back
     // across PCIe early and the later chunks amortise their launches
@@ -301,41 +293,31 @@ extern "C" int bj_lde_commit_h(const uint64_t* trace_h, uint32_t n_cols, uint32_
     const bool pin_lde = lde_h && is_pinned(lde_h);
     const size_t tn = n * n_cols;
     uint64_t *tr = nullptr, *mono = nullptr, *lde = nullptr, *lv = nullptr, *nodes = nullptr, *st = nullptr;
+    // The workspace's frees sit between two synchronisations: copies still in flight on s_in and
+    // s_out on an error path finish before the buffers go back (`before`, declared after the
+    // workspace, runs first), and the compute stream is drained after them (`after`).
+    struct Sync {
+        hipStream_t a, b;
+        ~Sync() {
+            (void)hipStreamSynchronize(a);
+            if (b) (void)hipStreamSynchronize(b);
+        }
+    } after{s_cmp, nullptr};
     // the library's own stream-ordered pool keeps this workspace mapped between calls
-    HIP_CHECK(bj::pool_alloc((void**)&tr, tn * 8, s_cmp), "pool_alloc");
-    HIP_CHECK(bj::pool_alloc((void**)&mono, tn * 8, s_cmp), "pool_alloc");
-    HIP_CHECK(bj::pool_alloc((void**)&lde, (tn << log_lde) * 8, s_cmp), "pool_alloc");
-    HIP_CHECK(bj::pool_alloc((void**)&lv, nl * 32, s_cmp), "pool_alloc");
-    HIP_CHECK(bj::pool_alloc((void**)&nodes, (nl - cap_size) * 32, s_cmp), "pool_alloc");
-    HIP_CHECK(bj::pool_alloc((void**)&st, nl * 32, s_cmp), "pool_alloc");
-    HIP_CHECK(hipStreamSynchronize(s_cmp), "sync");
-    struct Frees {
-        uint64_t** p[6];
-        hipStream_t s, s_in, s_out;
-        ~Frees() {
-            // copies still in flight on an error path finish before the buffers go back
-            (void)hipStreamSynchronize(s_in);
-            (void)hipStreamSynchronize(s_out);
-            for (auto q : p)
-                if (*q) (void)hipFreeAsync(*q, s);
-            (void)hipStreamSynchronize(s);
-        }
-    } frees{{&tr, &mono, &lde, &lv, &nodes, &st}, s_cmp, s_in, s_out};
-    std::vector<hipEvent_t> ev_in(n_chunks, nullptr), ev_cmp(n_chunks, nullptr);
-    struct Events {
-        std::vector<hipEvent_t>* v[2];
-        ~Events() {
-            for (auto e : v)
-                for (auto x : *e)
-                    if (x) (void)hipEventDestroy(x);
-        }
-    } evg{{&ev_in, &ev_cmp}};
-    for (uint32_t k = 0; k < n_chunks; k++) {
-        HIP_CHECK(hipEventCreateWithFlags(&ev_in[k], hipEventDisableTiming), "hipEventCreate");
-        HIP_CHECK(hipEventCreateWithFlags(&ev_cmp[k], hipEventDisableTiming), "hipEventCreate");
-    }
+    Workspace ws(s_cmp);
+    HIP_TRY(ws.alloc(&tr, tn), "pool_alloc");
+    HIP_TRY(ws.alloc(&mono, tn), "pool_alloc");
+    HIP_TRY(ws.alloc(&lde, tn << log_lde), "pool_alloc");
+    HIP_TRY(ws.alloc(&lv, nl * 4), "pool_alloc");
+    HIP_TRY(ws.alloc(&nodes, (nl - cap_size) * 4), "pool_alloc");
+    HIP_TRY(ws.alloc(&st, nl * 4), "pool_alloc");
+    HIP_TRY(hipStreamSynchronize(s_cmp), "sync");
+    Sync before{s_in, s_out};
+    Events ev_in, ev_cmp;
+    HIP_TRY(ev_in.make(n_chunks), "hipEventCreate");
+    HIP_TRY(ev_cmp.make(n_chunks), "hipEventCreate");
     // copy-out thread: the LDE rows of chunk k as soon as its compute is done.  It waits on the
-    // host until this thread has recorded ev_cmp[k], and stops early when the issuing side fails.
+    // host until this thread has recorded ev_cmp.ev[k], and stops early when the issuing side fails.
     hipError_t out_err = hipSuccess;
     std::mutex mu;
     std::condition_variable cv;
@@ -350,7 +332,7 @@ extern "C" int bj_lde_commit_h(const uint64_t* trace_h, uint32_t n_cols, uint32_
                 if (recorded <= k) return;
             }
             const uint32_t c0 = c_first[k], c = c_first[k + 1] - c0;
-            hipError_t e = hipStreamWaitEvent(s_out, ev_cmp[k], 0);
+            hipError_t e = hipStreamWaitEvent(s_out, ev_cmp.ev[k], 0);
             if (e == hipSuccess) e = d2h(sg, lde_h + (size_t)c0 * nd, lde + (size_t)c0 * nd, (size_t)c * nd * 8, pin_lde);
             if (e != hipSuccess) out_err = e;
         }
@@ -374,11 +356,11 @@ extern "C" int bj_lde_commit_h(const uint64_t* trace_h, uint32_t n_cols, uint32_
         const bool last = k + 1 == n_chunks;
         // host-to-device stays on the copy engine: the runtime's own path for pageable memory
         // keeps ~56 GB/s here beside the store kernels (staging it through our slots was slower)
-        HIP_CHECK(hipMemcpyAsync(tr + (size_t)c0 * n, trace_h + (size_t)c0 * n, (size_t)c * n * 8,
-                                 hipMemcpyHostToDevice, s_in),
-                  "memcpy trace");
-        HIP_CHECK(hipEventRecord(ev_in[k], s_in), "hipEventRecord");
-        HIP_CHECK(hipStreamWaitEvent(s_cmp, ev_in[k], 0), "hipStreamWaitEvent");
+        HIP_TRY(hipMemcpyAsync(tr + (size_t)c0 * n, trace_h + (size_t)c0 * n, (size_t)c * n * 8,
+                               hipMemcpyHostToDevice, s_in),
+                "memcpy trace");
+        HIP_TRY(hipEventRecord(ev_in.ev[k], s_in), "hipEventRecord");
+        HIP_TRY(hipStreamWaitEvent(s_cmp, ev_in.ev[k], 0), "hipStreamWaitEvent");
         if (int r = bj_lde_d(tr + (size_t)c0 * n, c, n, log_n, log_lde, mono + (size_t)c0 * n, lde + (size_t)c0 * nd,
                              s_cmp))
             return r;
@@ -386,7 +368,7 @@ extern "C" int bj_lde_commit_h(const uint64_t* trace_h, uint32_t n_cols, uint32_
         if (int r = bj_merkle_leaves_partial_d(lde + (size_t)c0 * nd, c, nd, nl, k ? st : nullptr, last ? lv : st,
                                                last ? 1 : 0, s_cmp))
             return r;
-        HIP_CHECK(hipEventRecord(ev_cmp[k], s_cmp), "hipEventRecord");
+        HIP_TRY(hipEventRecord(ev_cmp.ev[k], s_cmp), "hipEventRecord");
         {
             std::lock_guard<std::mutex> lk(mu);
             recorded = k + 1;
@@ -395,33 +377,27 @@ extern "C" int bj_lde_commit_h(const uint64_t* trace_h, uint32_t n_cols, uint32_
     }
     if (n_chunks == 0)
         if (int r = bj_merkle_leaves_d(lde, 0, nd, nl, lv, s_cmp)) return r;
-    hipEvent_t ev_leaves = nullptr, ev_nodes = nullptr;
-    HIP_CHECK(hipEventCreateWithFlags(&ev_leaves, hipEventDisableTiming), "hipEventCreate");
-    struct Ev {
-        hipEvent_t* e;
-        ~Ev() {
-            if (*e) (void)hipEventDestroy(*e);
-        }
-    } evl{&ev_leaves}, evn{&ev_nodes};
-    HIP_CHECK(hipEventCreateWithFlags(&ev_nodes, hipEventDisableTiming), "hipEventCreate");
-    HIP_CHECK(hipEventRecord(ev_leaves, s_cmp), "hipEventRecord");
+    Events ev_tree;
+    HIP_TRY(ev_tree.make(2), "hipEventCreate");
+    const hipEvent_t ev_leaves = ev_tree.ev[0], ev_nodes = ev_tree.ev[1];
+    HIP_TRY(hipEventRecord(ev_leaves, s_cmp), "hipEventRecord");
     if (int r = bj_merkle_nodes_d(lv, nl, cap_size, nodes, s_cmp)) return r;
-    HIP_CHECK(hipEventRecord(ev_nodes, s_cmp), "hipEventRecord");
+    HIP_TRY(hipEventRecord(ev_nodes, s_cmp), "hipEventRecord");
     out_thread.join();
-    if (out_err != hipSuccess) return hip_err(out_err, "memcpy lde");
+    if (out_err != hipSuccess) return hip_fail(out_err, "memcpy lde");
     // the leaf digests go out while the node levels are hashed
     if (leaves_h) {
-        HIP_CHECK(hipStreamWaitEvent(s_out, ev_leaves, 0), "hipStreamWaitEvent");
-        HIP_CHECK(d2h(sg, leaves_h, lv, nl * 32, is_pinned(leaves_h)), "memcpy leaves");
+        HIP_TRY(hipStreamWaitEvent(s_out, ev_leaves, 0), "hipStreamWaitEvent");
+        HIP_TRY(d2h(sg, leaves_h, lv, nl * 32, is_pinned(leaves_h)), "memcpy leaves");
     }
-    HIP_CHECK(hipStreamWaitEvent(s_out, ev_nodes, 0), "hipStreamWaitEvent");
-    if (nodes_h) HIP_CHECK(d2h(sg, nodes_h, nodes, (nl - cap_size) * 32, is_pinned(nodes_h)), "memcpy nodes");
+    HIP_TRY(hipStreamWaitEvent(s_out, ev_nodes, 0), "hipStreamWaitEvent");
+    if (nodes_h) HIP_TRY(d2h(sg, nodes_h, nodes, (nl - cap_size) * 32, is_pinned(nodes_h)), "memcpy nodes");
     if (cap_h) {
-        HIP_CHECK(hipMemcpyAsync(cap_h, nodes + 4 * (nl - 2 * (size_t)cap_size), (size_t)cap_size * 32,
-                                 hipMemcpyDeviceToHost, s_out),
-                  "memcpy cap");
+        HIP_TRY(hipMemcpyAsync(cap_h, nodes + 4 * (nl - 2 * (size_t)cap_size), (size_t)cap_size * 32,
+                               hipMemcpyDeviceToHost, s_out),
+                "memcpy cap");
     }
-    HIP_CHECK(hipStreamSynchronize(s_out), "sync");
-    HIP_CHECK(hipStreamSynchronize(s_in), "sync");
+    HIP_TRY(hipStreamSynchronize(s_out), "sync");
+    HIP_TRY(hipStreamSynchronize(s_in), "sync");
     return BJ_OK;
 }

@@ -165,7 +165,7 @@ int bj_pow_search_d(uint32_t hasher, const uint8_t* seed, size_t seed_len, uint3
     // the last nonce a window may hold is 2^64 - 2: 2^64 - 1 is BJ_POW_NO_RESULT (pow.rs:48, 61)
     if (n_nonces > BJ_POW_NO_RESULT - first_nonce)
         return bj::pow_einval("bj_pow_search_d", "first_nonce + n_nonces overflows");
-    const hipStream_t st = bj::stream_of(stream);
+    const hipStream_t st = bj::S(stream);
     if (hasher == BJ_HASHER_BLAKE2S)
         bj::launch<bj::B2sPow>(seed, seed_len, pow_bits, first_nonce, n_nonces, result_d, st);
     else

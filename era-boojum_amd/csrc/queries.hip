@@ -322,7 +322,7 @@ int bj_oracle_queries_d(const bj_query_oracle_t* oracles, uint32_t n_oracles, co
         return bj::set_error(BJ_EINVAL, "bj_oracle_queries_d: out_words below n_queries * the oracles' record words");
     const uint32_t bx = n_queries < bj::QUERY_MAX_BLOCKS_X ? n_queries : bj::QUERY_MAX_BLOCKS_X;
     hipLaunchKernelGGL(bj::oracle_queries_kernel, dim3(bx, n_oracles), dim3(bj::QUERY_THREADS), 0,
-                       bj::stream_of(stream), a, indices_d, n_queries, out_d, status_d);
+                       bj::S(stream), a, indices_d, n_queries, out_d, status_d);
     return bj::ok_or(hipGetLastError(), "oracle queries");
 }
 

@@ -272,7 +272,7 @@ int bj_quotient_copy_permutation_d(const uint64_t* vars, size_t vars_stride, con
     const hipError_t e = bj::launch_quotient_cp(vars, vars_stride, sigmas, sigmas_stride, stage2, stage2_stride, n_cols,
                                                 log_n, log_q, non_residues, bj::ext2::canon2(beta0, beta1),
                                                 bj::ext2::canon2(gamma0, gamma1), alphas, dst0, dst1,
-                                                bj::stream_of(stream));
+                                                bj::S(stream));
     return bj::ok_or(e, "quotient copy permutation");
 }
 
@@ -290,7 +290,7 @@ int bj_quotient_lookup_term_d(const uint64_t* const* srcs, uint32_t n_src, const
         return bj::set_error(BJ_EINVAL, "bj_quotient_lookup_term_d: null source column");
     const size_t total = (size_t)1 << (log_n + log_q);
     hipLaunchKernelGGL(bj::quotient_lookup_kernel, dim3((unsigned)((total + bj::LT_THREADS - 1) / bj::LT_THREADS)),
-                       dim3(bj::LT_THREADS), 0, bj::stream_of(stream), k, n_src, bj::ext2::canon2(beta0, beta1), e_c0,
+                       dim3(bj::LT_THREADS), 0, bj::S(stream), k, n_src, bj::ext2::canon2(beta0, beta1), e_c0,
                        e_c1, f, bj::ext2::canon2(alpha0, alpha1), total, dst0, dst1);
     return bj::ok_or(hipGetLastError(), "quotient lookup term");
 }
@@ -316,7 +316,7 @@ int bj_quotient_divide_vanishing_d(uint64_t* dst0, uint64_t* dst1, uint32_t log_
     if (const int rc = bj_vanishing_inverses_h(log_n, log_q, k.inv)) return rc;
     const size_t total = (size_t)1 << (log_n + log_q);
     hipLaunchKernelGGL(bj::quotient_divide_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       bj::stream_of(stream), k, log_n, total, dst0, dst1);
+                       bj::S(stream), k, log_n, total, dst0, dst1);
     return bj::ok_or(hipGetLastError(), "quotient divide by vanishing");
 }
 

@@ -356,7 +356,7 @@ int bj_copy_permutation_d(const uint64_t* vars, size_t vars_stride, const uint64
     const hipError_t e = bj::launch_copy_permutation(vars, vars_stride, sigmas, sigmas_stride, n_cols, log_n,
                                                      non_residues, bj::ext2::canon2(beta0, beta1),
                                                      bj::ext2::canon2(gamma0, gamma1), log_q, out, out_stride, status_d,
-                                                     bj::stream_of(stream));
+                                                     bj::S(stream));
     return bj::ok_or(e, "copy permutation");
 }
 
@@ -372,7 +372,7 @@ int bj_lookup_encoding_d(const uint64_t* const* srcs, uint32_t n_src, const uint
     if (!bj::fill_lookup_sources(k, srcs, n_src, g))
         return bj::set_error(BJ_EINVAL, "bj_lookup_encoding_d: null source column");
     const size_t n = (size_t)1 << log_n;
-    hipStream_t st = bj::stream_of(stream);
+    hipStream_t st = bj::S(stream);
     hipError_t e = hipMemsetAsync(status_d, 0, 4 * sizeof(uint64_t), st);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(bj::lookup_encoding_kernel, dim3((unsigned)((n + bj::LK_TILE - 1) / bj::LK_TILE)),

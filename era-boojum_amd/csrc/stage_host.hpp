@@ -1,39 +1,15 @@
 // What the prover-stage sources (fri.hip, deep.hip, stage2.hip, quotient.hip, gates.hip, witness.hip,
-// queries.hip, pow.hip) share on the host: the BJ_EHIP return, the stream cast, stream-ordered
-// scratch, the domain checks and the constants that travel by value in kernel arguments.  A new
-// stage takes these from here and its Ext2 from ext2.hpp.  Everything has internal linkage, so the
-// library exports nothing of it.
+// queries.hip, pow.hip) add to host.hpp on the host: the domain checks and the constants that
+// travel by value in kernel arguments.  A new stage takes the error returns, the stream cast and
+// its scratch from host.hpp, these from here and its Ext2 from ext2.hpp.  Everything has internal
+// linkage, so the library exports nothing of it.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdio.h>
 #include "gl.hpp"
-#include "bj_internal.hpp"
-#include "../../include/boojum_mi355x.h"
+#include "host.hpp"
 
 namespace bj {
 
 namespace {
-
-// BJ_EHIP with "<what>: <the runtime's text>" as the calling thread's bj_last_error()
-int hip_error(hipError_t e, const char* what) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-    return set_error(BJ_EHIP, msg);
-}
-int ok_or(hipError_t e, const char* what) { return e == hipSuccess ? BJ_OK : hip_error(e, what); }
-
-hipStream_t stream_of(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
-
-// stream-ordered scratch from the library's pool, freed on the same stream when it goes out of scope
-struct Scratch {
-    uint64_t* p = nullptr;
-    hipStream_t st;
-    explicit Scratch(hipStream_t s) : st(s) {}
-    hipError_t alloc(size_t words) { return pool_alloc((void**)&p, words * 8, st); }
-    ~Scratch() {
-        if (p) (void)hipFreeAsync(p, st);
-    }
-};
 
 // the size checks of a domain of 2^log_n points and of its 2^log_q cosets; NULL when they are fine
 const char* bad_log_n(uint32_t log_n) {

@@ -190,7 +190,7 @@ int bj_copy_hint_upload_d(const uint64_t* words, uint32_t n_cols, uint64_t n_row
     }
     if (e != hipSuccess) {
         delete h;
-        return bj::hip_error(e, "copy hint upload");
+        return bj::hip_fail(e, "copy hint upload");
     }
     h->magic = bj::HINT_MAGIC;
     h->n_cols = n_cols;
@@ -240,7 +240,7 @@ int bj_materialize_columns_d(const void* hint, const uint64_t* all_values, uint6
     if (padded * col_tiles > 0x7fffffffull)
         return bj::set_error(BJ_EINVAL, "bj_materialize_columns_d: more workgroups than one grid holds");
     hipLaunchKernelGGL(bj::materialize_kernel, dim3((unsigned)(padded * col_tiles)), dim3(bj::WIT_THREADS), 0,
-                       bj::stream_of(stream), h->cells_d, h->n_cols, (size_t)h->n_rows, (uint32_t)row_blocks,
+                       bj::S(stream), h->cells_d, h->n_cols, (size_t)h->n_rows, (uint32_t)row_blocks,
                        (uint32_t)col_tiles, all_values, out, out_stride);
     return bj::ok_or(hipGetLastError(), "materialize columns");
 }
@@ -254,7 +254,7 @@ int bj_materialize_multiplicities_d(const uint32_t* mult_u32, uint64_t len, uint
     if (blocks > 0x7fffffffull)
         return bj::set_error(BJ_EINVAL, "bj_materialize_multiplicities_d: more workgroups than one grid holds");
     hipLaunchKernelGGL(bj::multiplicities_kernel, dim3((unsigned)blocks), dim3(bj::WIT_THREADS), 0,
-                       bj::stream_of(stream), mult_u32, (size_t)len, out, (size_t)n_rows);
+                       bj::S(stream), mult_u32, (size_t)len, out, (size_t)n_rows);
     return bj::ok_or(hipGetLastError(), "materialize multiplicities");
 }
 
@@ -268,21 +268,22 @@ int bj_permutation_polys_d(const uint32_t* prev, uint32_t n_cols, uint64_t n_row
     if (n_cols == 0 || n_cols > 65535 || (uint64_t)n_cols * n > ((uint64_t)1 << 32))
         return bj::set_error(BJ_EINVAL, "bj_permutation_polys_d: n_cols outside 1..65535 or more than 2^32 cells");
     if (out_stride < n) return bj::set_error(BJ_EINVAL, "bj_permutation_polys_d: out_stride is below n_rows");
-    hipStream_t st = bj::stream_of(stream);
+    hipStream_t st = bj::S(stream);
     const size_t half = log_n ? (size_t)(n >> 1) : 0;
     std::vector<uint64_t> k(n_cols);
     for (uint32_t c = 0; c < n_cols; c++) k[c] = gl::canon(non_residues[c]);
-    bj::Scratch tab(st);
-    hipError_t e = tab.alloc(n_cols + half);
-    if (e != hipSuccess) return bj::hip_error(e, "permutation polys table");
+    bj::Workspace ws(st);
+    uint64_t* tab = nullptr;
+    hipError_t e = ws.alloc(&tab, n_cols + half);
+    if (e != hipSuccess) return bj::hip_fail(e, "permutation polys table");
     // k is pageable host memory: the copy has left it when the call returns
-    e = hipMemcpyAsync(tab.p, k.data(), n_cols * sizeof(uint64_t), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(tab, k.data(), n_cols * sizeof(uint64_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && log_n) e = bj::launch_twiddles_natural(tab.p + n_cols, log_n, false, st);
+    if (e == hipSuccess && log_n) e = bj::launch_twiddles_natural(tab + n_cols, log_n, false, st);
     if (e == hipSuccess) {
         const uint64_t blocks = (n + bj::WIT_THREADS - 1) / bj::WIT_THREADS;
         hipLaunchKernelGGL(bj::permutation_polys_kernel, dim3((unsigned)blocks, n_cols), dim3(bj::WIT_THREADS), 0, st,
-                           prev, n_cols, log_n, tab.p, out, out_stride);
+                           prev, n_cols, log_n, tab, out, out_stride);
         e = hipGetLastError();
     }
     return bj::ok_or(e, "permutation polys");
