@@ -122,6 +122,7 @@ SIGNATURES = {
     "bj_quotient_divide_vanishing_d": ([_vp, _vp, _u32, _u32, _vp], _int),
     "bj_vanishing_inverses_h": ([_u32, _u32, _u64p], _int),
     "bj_gate_set_check_h": ([_u64p, _sz, _u64p], _int),
+    "bj_gate_native_info_h": ([_u32, _u64p], _int),
     "bj_gate_set_upload_d": ([_u64p, _sz, ctypes.POINTER(_vp)], _int),
     "bj_gate_set_release": ([_vp], _int),
     "bj_quotient_gate_terms_d": ([_vp, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _u32, _u32, _u32,
@@ -145,6 +146,8 @@ SIGNATURES = {
     "bj_gl_op_d": ([_int, _vp, _vp, _vp, _sz, _vp], _int),
 }
 
+# Added after 2.6 and detected by symbol: a library without one of these still loads.
+OPTIONAL = ("bj_gate_native_info_h",)
 
 
 class CommInfo(ctypes.Structure):
@@ -182,6 +185,8 @@ def load():
                 "`make -C era-boojum_amd` (or __graft_entry__.build())" % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (args, res) in SIGNATURES.items():
+            if name in OPTIONAL and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = res

@@ -14,6 +14,9 @@ gpu_synthesizer/mod.rs captures from an evaluator's `evaluate_once`:
   reference does for a CSGeometry;
 * `compile_gate_set` (host only): slot allocation by liveness, the split into launches and the
   upload image; `GateSet`: validation (bj_gate_set_check_h) and the one upload;
+* native segments: an evaluator that declares a `native_kind` (`Poseidon2FlattenedGate`, whose
+  capture passes every cap of a launch) is not captured; it gets a segment of its own that names the
+  kind, and the library runs a written-out kernel on it (csrc/gates_poseidon2.hpp);
 * `evaluate_gate_terms`: dst += the gate terms, one launch per segment;
 * `check_if_satisfied` -> `SatisfiabilityReport`: the reference's check_if_satisfied
   (cs/implementations/satisfiability_test.rs:15-353) over the trace columns, on the device
@@ -26,6 +29,8 @@ integers) to give the values; each restates the reference's `evaluate_once`.  Th
 fallback: nothing here evaluates a program.
 """
 import ctypes
+import os
+import re
 
 import numpy as np
 import torch
@@ -39,6 +44,7 @@ MAX_INSTRUCTIONS = 4096     # BJ_GATE_MAX_INSTRUCTIONS, also the writes and the 
 MAX_GATES = 64              # BJ_GATE_MAX_GATES
 MAX_SEGMENTS = 64           # BJ_GATE_MAX_SEGMENTS
 MAGIC = 0x3153455441474A42  # "BJGATES1"
+KIND_INTERPRETED, KIND_POSEIDON2 = 0, 1   # word [7] of a segment head
 
 _KINDS = ("VariablePoly", "WitnessPoly", "ConstantPoly", "TemporaryValue", "ConstantValue")
 _RELATIONS = ("Add", "Double", "Sub", "Negate", "Mul", "Square", "Inverse")
@@ -218,6 +224,35 @@ def capture(evaluator):
     return GateProgram(ctx.relations, dst.writes, evaluator.num_quotient_terms, evaluator)
 
 
+class NativeGateProgram:
+    """What stands for the capture of an evaluator with a native kind: nothing is recorded, the
+    library knows the gate."""
+    relations = writes = None
+
+    def __init__(self, evaluator):
+        if not getattr(evaluator, "native_kind", KIND_INTERPRETED):
+            raise ValueError("the evaluator declares no native kind")
+        self.evaluator = evaluator
+        self.num_quotient_terms = evaluator.num_quotient_terms
+
+
+def program_of(evaluator):
+    """The program a placement carries: the capture, or for a native kind its stand-in."""
+    if getattr(evaluator, "native_kind", KIND_INTERPRETED):
+        return NativeGateProgram(evaluator)
+    return capture(evaluator)
+
+
+def native_gate_info(kind):
+    """bj_gate_native_info_h: (cells, terms, degree, most witness cells) of a native kind, or None
+    when the library is older than native segments or does not know the kind."""
+    fn = getattr(load(), "bj_gate_native_info_h", None)
+    out = (ctypes.c_uint64 * 4)()
+    if fn is None or fn(kind, out) != 0:
+        return None
+    return tuple(int(v) for v in out)
+
+
 # ------------------------------------------------------------------ placement
 class PerChunkOffset:
     """cs/traits/evaluator.rs PerChunkOffset."""
@@ -269,7 +304,7 @@ def layout_general_purpose(evaluators_with_paths, geometry):
     """The general-purpose gates of a set: (evaluator, selector path) pairs in evaluation order ->
     placements with the geometry's repetition counts and constants_offset = len(path)
     (prover.rs:996-1015)."""
-    return [GatePlacement(capture(e), e.num_repetitions_in_geometry(geometry), e.per_chunk_offset, path)
+    return [GatePlacement(program_of(e), e.num_repetitions_in_geometry(geometry), e.per_chunk_offset, path)
             for e, path in evaluators_with_paths]
 
 
@@ -280,7 +315,7 @@ def specialized_placement(evaluator, num_repetitions, share_constants, initial_o
     with share_constants the repetitions do not advance the constants (:750-752)."""
     v, w, c = evaluator.principal_width
     per = PerChunkOffset(v, w, 0 if share_constants else c)
-    return GatePlacement(capture(evaluator), num_repetitions, per, (),
+    return GatePlacement(program_of(evaluator), num_repetitions, per, (),
                          constants_for_gates_over_general_purpose_columns, initial_offset)
 
 
@@ -342,10 +377,11 @@ class _Segment:
         self.imm_index = {}
         self.terms = 0
         self.depth = 0
+        self.kind = KIND_INTERPRETED
 
     def words(self):
         head = [len(self.desc) // 8, len(self.instr), len(self.writes), len(self.imm), self.alpha_base, self.terms,
-                self.depth, 0]
+                self.depth, self.kind]
         return head + self.desc + self.instr + self.writes + self.imm
 
 
@@ -393,10 +429,41 @@ def _encode_gate(seg, pl, cap):
     return True
 
 
+def _native_kind(pl):
+    return getattr(pl.program.evaluator, "native_kind", KIND_INTERPRETED)
+
+
+def _encode_native(seg, pl, kind):
+    """The one gate of a native segment: no program, the descriptor's words [2] .. [6] as for an
+    interpreted gate, [1] the terms per repetition with no writes behind them, [7] the evaluator's
+    num_witness_columns_used."""
+    info = native_gate_info(kind)
+    if info is None:   # a library from before native segments: the gate can only be refused
+        raise ValueError("one gate exceeds the caps of a launch")
+    cells, terms, _, most_witnesses = info
+    evaluator = pl.program.evaluator
+    nw = evaluator.num_witness_columns_used
+    bases, per = pl.bases(), pl.per_chunk_offset.as_tuple()
+    if terms != evaluator.num_quotient_terms or not 0 <= nw <= most_witnesses:
+        raise ValueError("%s does not match the library's native kind %d" % (evaluator.name, kind))
+    if per[0] < cells - nw or per[1] < nw:
+        raise ValueError("a repetition of %s is narrower than its %d cells" % (evaluator.name, cells))
+    if len(pl.selector_path) > 63:
+        raise ValueError("selector path too long")
+    mask = sum(1 << i for i, b in enumerate(pl.selector_path) if b)
+    seg.kind = kind
+    seg.desc += [0, terms << 32, pl.num_repetitions | len(pl.selector_path) << 32, mask,
+                 bases[0] | per[0] << 32, bases[1] | per[1] << 32, bases[2] | per[2] << 32, nw]
+    seg.terms = pl.num_terms()
+    seg.depth = len(pl.selector_path)
+
+
 def compile_gate_set(placements, slot_cap=MAX_SLOTS):
     """Placements in evaluation order -> the upload image, a list of u64 words
     (include/boojum_mi355x.h, "quotient gate terms").  Gates fill a segment until a cap of one launch
-    would be passed; the next segment's alpha base carries the challenge index on.  Host only."""
+    would be passed; the next segment's alpha base carries the challenge index on.  A placement
+    whose evaluator declares a native kind closes the segment before it and takes one of its own,
+    uncaptured.  Host only."""
     placements = list(placements)
     if not placements:
         raise ValueError("a gate set holds at least one gate with quotient terms")
@@ -404,6 +471,14 @@ def compile_gate_set(placements, slot_cap=MAX_SLOTS):
     for pl in placements:
         if pl.program.num_quotient_terms == 0:
             raise ValueError("a gate without quotient terms never reaches the library (prover.rs:922-994)")
+        if _native_kind(pl):
+            if seg.desc:
+                segments.append(seg)
+                seg = _Segment(seg.alpha_base + seg.terms)
+            _encode_native(seg, pl, _native_kind(pl))
+            segments.append(seg)
+            seg = _Segment(seg.alpha_base + seg.terms)
+            continue
         if not _encode_gate(seg, pl, slot_cap):
             if not seg.desc:
                 raise ValueError("one gate exceeds the caps of a launch")
@@ -411,7 +486,8 @@ def compile_gate_set(placements, slot_cap=MAX_SLOTS):
             seg = _Segment(seg.alpha_base + seg.terms)
             if not _encode_gate(seg, pl, slot_cap):
                 raise ValueError("one gate exceeds the caps of a launch")
-    segments.append(seg)
+    if seg.desc:
+        segments.append(seg)
     image = [MAGIC, len(segments)] + [0] * len(segments)
     for i, s in enumerate(segments):
         image[2 + i] = len(image)
@@ -671,6 +747,7 @@ class Evaluator:
     num_quotient_terms = 1
     max_constraint_degree = 2
     principal_width = (0, 0, 0)
+    native_kind = KIND_INTERPRETED   # a kind the library evaluates without a capture, or 0
 
     @property
     def per_chunk_offset(self):
@@ -854,6 +931,160 @@ class ConditionalSwapGate(Evaluator):
                 r.mul_and_accumulate_into(t, other)
                 r.sub_assign(result)
                 dst.push_evaluation_result(r)
+
+
+# Poseidon2 over Goldilocks as the reference parameterises it (poseidon2/params.rs:8-136): the 4x4
+# block and the diagonal shifts, the matrices built from them, and the round constants of
+# csrc/poseidon2_rc.inc (ROUND_CONSTANTS_ALIGNED_PER_ROUND: rounds 0..3 and 26..29 are the full
+# rounds', element 0 of rounds 4..25 the partial rounds').
+POSEIDON2_M4 = ((5, 7, 1, 3), (4, 6, 1, 1), (1, 3, 5, 7), (1, 1, 4, 6))
+POSEIDON2_SHIFTS = (4, 14, 11, 8, 0, 5, 2, 9, 13, 6, 3, 12)
+_POSEIDON2_RC = None
+
+
+def poseidon2_external_matrix():
+    """EXTERNAL_MDS_MATRIX (params.rs:63-94): block circulant, the diagonal blocks doubled."""
+    return [[(2 if i // 4 == j // 4 else 1) * POSEIDON2_M4[i % 4][j % 4] for j in range(12)] for i in range(12)]
+
+
+def poseidon2_inner_matrix():
+    """INNER_ROUNDS_MATRIX (params.rs:96-105): ones, the diagonal 2^shift + 1."""
+    return [[(1 << POSEIDON2_SHIFTS[i]) + 1 if i == j else 1 for j in range(12)] for i in range(12)]
+
+
+def poseidon2_round_constants():
+    """The 30 x 12 round constants, read once from the table the kernels are built from."""
+    global _POSEIDON2_RC
+    if _POSEIDON2_RC is None:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc", "poseidon2_rc.inc")
+        with open(path) as f:
+            values = [int(v) for v in re.findall(r"(\d+)ULL", f.read())]
+        if len(values) != 360:
+            raise ValueError("%s: expected 30 x 12 round constants" % path)
+        _POSEIDON2_RC = [values[12 * r:12 * r + 12] for r in range(30)]
+    return _POSEIDON2_RC
+
+
+def _small_pow_7(x):
+    """PrimeFieldLike::small_pow(7) (field_like.rs:92-101): x^2, x^4, x^6, x^7; a new value."""
+    tmp = x.copy()
+    tmp.square()
+    pow2 = tmp.copy()
+    tmp.square()
+    tmp.mul_assign(pow2)
+    tmp.mul_assign(x)
+    return tmp
+
+
+def _matrix_mul_naive(state, matrix, field):
+    """dst_i = sum_j state_j * coeff_ij, from zero, by mul_and_accumulate_into (poseidon2.rs:247-255)."""
+    out = []
+    for row in matrix:
+        tmp = field.zero()
+        for src, coeff in zip(state, row):
+            tmp.mul_and_accumulate_into(src, field.constant(coeff))
+        out.append(tmp)
+    return out
+
+
+class Poseidon2FlattenedGate(Evaluator):
+    """Poseidon2RoundFunctionFlattenedEvaluator<F, 8, 12, 4> over Goldilocks (poseidon2.rs:166-403):
+    the permutation of variables 0..11 equals variables 12..23, every S-box layer "reset" by committed
+    cells.  118 terms of degree 7 in push order: 3 x 12 resets of the first half, 22 of the partial
+    rounds, 4 x 12 of the second half, 12 output terms.  S-box output cell s (0..105) reads witness
+    column s while s < num_witness_columns_used and variable column 24 + s - num_witness_columns_used
+    after that (:225-236).  The matrices are applied naively with constant coefficients, as the
+    reference does, so the capture is its IR -- which passes every cap of a launch; the gate is a
+    native kind and compile_gate_set does not capture it."""
+    name = "poseidon2_flattened"
+    native_kind = KIND_POSEIDON2
+    num_quotient_terms = 118
+    max_constraint_degree = 7
+    STATE_WIDTH, HALF_NUM_FULL_ROUNDS, NUM_PARTIAL_ROUNDS = 12, 4, 22
+    TOTAL_NUM_VARIABLES = 130   # total_num_variables (:430-437)
+
+    def __init__(self, num_copiable_columns_used, num_witness_columns_used):
+        self.num_copiable_columns_used = int(num_copiable_columns_used)
+        self.num_witness_columns_used = int(num_witness_columns_used)
+        if not 0 <= self.num_witness_columns_used <= self.TOTAL_NUM_VARIABLES - 2 * self.STATE_WIDTH:
+            raise ValueError("at most 106 cells of the gate can be witness columns")
+        if self.num_copiable_columns_used + self.num_witness_columns_used < self.TOTAL_NUM_VARIABLES:
+            raise ValueError("the gate needs 130 cells (:231, :309, :361)")
+        self.principal_width = (self.num_copiable_columns_used, self.num_witness_columns_used, 0)
+
+    def num_repetitions_in_geometry(self, geometry):
+        """The min of the copiable and the witness limit (:84-104)."""
+        reps = geometry.num_columns_under_copy_permutation // self.num_copiable_columns_used
+        if self.num_witness_columns_used:
+            reps = min(reps, geometry.num_witness_columns // self.num_witness_columns_used)
+        return reps
+
+    def num_required_constants_in_geometry(self, geometry):
+        return 0
+
+    @classmethod
+    def compute_strategy(cls, geometry):
+        """Poseidon2FlattenedGate::compute_strategy (:502-528): (instances, (copiable, witness
+        columns per instance))."""
+        num_copiable, num_witnesses = geometry.num_columns_under_copy_permutation, geometry.num_witness_columns
+        max_instances = min(num_copiable // (2 * cls.STATE_WIDTH),
+                            (num_copiable + num_witnesses) // cls.TOTAL_NUM_VARIABLES)
+        if max_instances <= 0:
+            raise ValueError("can not allocate a gate, need at least %d copiable vars and %d vars + witnesses in total"
+                             % (2 * cls.STATE_WIDTH, cls.TOTAL_NUM_VARIABLES))
+        in_witness_per_copy = num_witnesses // max_instances
+        return max_instances, (cls.TOTAL_NUM_VARIABLES - in_witness_per_copy, in_witness_per_copy)
+
+    def evaluate_once(self, src, dst, shared):
+        sw, half = self.STATE_WIDTH, self.HALF_NUM_FULL_ROUNDS
+        field, rc = src.field(), poseidon2_round_constants()
+        external, inner = poseidon2_external_matrix(), poseidon2_inner_matrix()
+        full_round_constants = rc[:half] + rc[half + self.NUM_PARTIAL_ROUNDS:]
+        partial_round_constants = [rc[half + r][0] for r in range(self.NUM_PARTIAL_ROUNDS)]
+        state = [src.get_variable_value(i) for i in range(sw)]
+        output = [src.get_variable_value(sw + i) for i in range(sw)]   # the output is placed early
+        offsets = {"witness": 0, "copiable": 2 * sw}
+
+        def sbox_out_var():   # witness columns first, then copiable ones (:225-236)
+            if offsets["witness"] < self.num_witness_columns_used:
+                offsets["witness"] += 1
+                return src.get_witness_value(offsets["witness"] - 1)
+            offsets["copiable"] += 1
+            return src.get_variable_value(offsets["copiable"] - 1)
+
+        def reset(state):
+            cells = []
+            for value in state:
+                cell = sbox_out_var()
+                contribution = value.copy()
+                contribution.sub_assign(cell)
+                dst.push_evaluation_result(contribution)
+                cells.append(cell)
+            return cells
+
+        def full_round(state, round):
+            for i in range(sw):
+                state[i].add_assign(field.constant(full_round_constants[round][i]))
+                state[i] = _small_pow_7(state[i])
+            return _matrix_mul_naive(state, external, field)
+
+        for round in range(half):
+            state = reset(state) if round else _matrix_mul_naive(state, external, field)
+            state = full_round(state, round)
+        for round in range(self.NUM_PARTIAL_ROUNDS):
+            state[0].add_assign(field.constant(partial_round_constants[round]))
+            cell = sbox_out_var()
+            contribution = state[0].copy()
+            contribution.sub_assign(cell)
+            dst.push_evaluation_result(contribution)
+            state[0] = _small_pow_7(cell)
+            state = _matrix_mul_naive(state, inner, field)
+        for round in range(half):
+            state = full_round(reset(state), half + round)
+        for value, out in zip(state, output):
+            contribution = out.copy()
+            contribution.sub_assign(value)
+            dst.push_evaluation_result(contribution)
 
 
 def library():

@@ -26,19 +26,24 @@
 // Image (u64 words, built by the caller, checked by check_image below, uploaded once):
 //   [0] GT_MAGIC  [1] number of segments S  [2 .. 2 + S) word offset of each segment
 //   segment: [0] gates G  [1] instructions I  [2] writes W  [3] immediates M  [4] alpha base
-//            [5] terms (sum over gates of repetitions * writes)  [6] selector columns read  [7] 0
+//            [5] terms (sum over gates of repetitions * writes)  [6] selector columns read
+//            [7] kind: 0 interpreted, 1 native Poseidon2 flattened gate (gates_poseidon2.hpp)
 //            G descriptors of 8 words, I instructions, W writes, M immediates
 //   descriptor: [0] instr begin | end << 32   [1] write begin | end << 32
 //               [2] repetitions | path length << 32   [3] path bit mask (bit i set: take column i,
 //               clear: 1 - column i)   [4] variables base | per repetition << 32
 //               [5] witnesses base | per repetition << 32   [6] constants base | per repetition << 32
-//               [7] 0
+//               [7] 0; in a native segment num_witness_columns_used
 //   instruction: opcode | slot << 8 | a << 16 | b << 40;  operand (24 bits): kind << 21 | index
 //   kinds: 0 VariablePoly, 1 WitnessPoly, 2 ConstantPoly, 3 slot, 4 immediate (index into M)
 //   opcodes: Relation's order -- 0 Add, 1 Double, 2 Sub, 3 Negate, 4 Mul, 5 Square; 6 Inverse is
 //   refused.  No evaluator in cs/gates records it: the three textual hits
 //   (fma_gate_without_constant.rs:353, fma_gate_in_extension_without_constant.rs:451,
 //   zero_check.rs:539) are all inside witness-resolution closures, not evaluate_once.
+//
+// A native segment holds one gate of a kind the library has a written-out kernel for: G = 1,
+// I = W = M = 0, the descriptor's [0] is 0 and its [1] is 0 | terms per repetition << 32 with no
+// writes behind it, [2] .. [6] keep their meaning.  The two entry points dispatch on the kind.
 //
 // One call launches one segment.  A gate set over the caps is split into segments by the caller,
 // which is exact because the call adds to the accumulator and a segment carries its alpha base.
@@ -48,6 +53,7 @@
 // trace rows and reports the count and the first failing (row, term) in a status record.
 #include <hip/hip_runtime.h>
 #include <new>
+#include "ext2.hpp"
 #include "gl.hpp"
 #include "stage_host.hpp"
 
@@ -189,6 +195,24 @@ __global__ void gate_check_begin_kernel(unsigned long long* __restrict__ status)
     if (threadIdx.x < 4) status[threadIdx.x] = threadIdx.x == 1 ? GC_NONE : 0;
 }
 
+// A lane's failures (their number and the first k, on row L) into the record: one add and one min
+// per wave that saw a failure.
+__device__ __forceinline__ void check_combine(uint64_t count, uint32_t first, size_t L,
+                                              unsigned long long* __restrict__ status) {
+    unsigned long long key = count ? ((unsigned long long)L << 32) | first : GC_NONE;
+    unsigned long long sum = count;
+#pragma unroll
+    for (uint32_t o = GC_WAVE / 2; o; o >>= 1) {
+        sum += __shfl_down(sum, o, GC_WAVE);
+        const unsigned long long other = __shfl_down(key, o, GC_WAVE);
+        key = other < key ? other : key;
+    }
+    if ((threadIdx.x & (GC_WAVE - 1)) == 0 && sum) {
+        atomicAdd(&status[0], sum);
+        atomicMin(&status[1], key);
+    }
+}
+
 template <bool VALUE>
 __global__ __launch_bounds__(GT_THREADS) void gate_check_kernel(const uint64_t* __restrict__ seg, Cols cols,
                                                                 uint64_t row_begin, uint64_t n_rows,
@@ -281,21 +305,10 @@ __global__ __launch_bounds__(GT_THREADS) void gate_check_kernel(const uint64_t* 
             off[2] += (uint32_t)(dc >> 32);
         }
     }
-    if constexpr (!VALUE) {
-        unsigned long long key = count ? ((unsigned long long)L << 32) | first : GC_NONE;
-        unsigned long long sum = count;
-#pragma unroll
-        for (uint32_t o = GC_WAVE / 2; o; o >>= 1) {
-            sum += __shfl_down(sum, o, GC_WAVE);
-            const unsigned long long other = __shfl_down(key, o, GC_WAVE);
-            key = other < key ? other : key;
-        }
-        if ((threadIdx.x & (GC_WAVE - 1)) == 0 && sum) {
-            atomicAdd(&status[0], sum);
-            atomicMin(&status[1], key);
-        }
-    }
+    if constexpr (!VALUE) check_combine(count, first, L, status);
 }
+
+#include "gates_poseidon2.hpp"
 
 // ------------------------------------------------------------------ host side: the image's checks
 struct Need {
@@ -310,6 +323,7 @@ struct GateSet {
     Need need;
     uint64_t n_segments;
     uint64_t seg_offset[BJ_GATE_MAX_SEGMENTS];
+    uint64_t seg_kind[BJ_GATE_MAX_SEGMENTS];
 };
 
 int bad(const char* why) {
@@ -330,7 +344,34 @@ bool operand_ok(uint32_t operand, uint64_t n_imm, uint32_t written, const uint64
     return true;
 }
 
-int check_image(const uint64_t* image, size_t words, Need& need, uint64_t* seg_offset) {
+// A native segment (kind != 0): one gate, no program, the kind's own term count and cell split.
+int check_native(const uint64_t* seg, Need& need) {
+    const uint64_t G = seg[0], I = seg[1], W = seg[2], M = seg[3], terms = seg[5], sel = seg[6], kind = seg[7];
+    if (kind != p2g::KIND) return bad("unknown native segment kind");
+    if (G != 1) return bad("a native segment holds exactly one gate");
+    if (I || W || M) return bad("a native segment carries no instructions, writes or immediates");
+    const uint64_t* d = seg + GT_HDR;
+    const uint64_t reps = d[2] & 0xffffffff, depth = d[2] >> 32, nw = d[7];
+    if (d[0] != 0 || d[1] != (uint64_t)p2g::TERMS << 32) return bad("a native gate's instruction or write range is malformed");
+    if (reps == 0 || reps > (1u << 20)) return bad("num_repetitions outside 1..2^20");
+    if (depth > GT_SEL || (d[3] >> depth)) return bad("malformed selector path");
+    if (terms != p2g::TERMS * reps) return bad("a native segment's term count is not 118 per repetition");
+    if (sel != depth) return bad("a segment's selector columns are not its deepest path");
+    if (nw > p2g::MAX_WITNESS_CELLS) return bad("num_witness_columns_used exceeds the gate's 106 S-box output cells");
+    const uint64_t width[3] = {p2g::CELLS - nw, nw, 0};
+    for (int k = 0; k < 3; k++) {
+        const uint64_t b = d[4 + k] & 0xffffffff, per = d[4 + k] >> 32;
+        if (b > (1u << 20) || per > (1u << 10)) return bad("a column offset is out of range");
+        if (per < width[k]) return bad("a repetition of the native gate is narrower than its cells");
+        const uint64_t reach = b + per * (reps - 1) + width[k];  // columns needed at the largest repetition
+        if (reach > ((uint64_t)1 << 31)) return bad("a column offset is out of range");
+        if (width[k] && reach > need.cols[k]) need.cols[k] = reach;
+    }
+    if (sel > need.cols[K_CONST]) need.cols[K_CONST] = sel;
+    return BJ_OK;
+}
+
+int check_image(const uint64_t* image, size_t words, Need& need, uint64_t* seg_offset, uint64_t* seg_kind) {
     need = Need{{0, 0, 0}, 0, 0};
     if (!image) return bad("null image");
     if (words < 2 || image[0] != GT_MAGIC) return bad("not a gate-set image");
@@ -348,8 +389,14 @@ int check_image(const uint64_t* image, size_t words, Need& need, uint64_t* seg_o
         if (W > GT_INSTRS || M > GT_INSTRS) return bad("a segment's writes or immediates exceed BJ_GATE_MAX_INSTRUCTIONS");
         if (words - at < GT_HDR + G * GT_DESC + I + W + M) return bad("truncated segment");
         if (sel > GT_SEL) return bad("selector depth exceeds BJ_GATE_MAX_SELECTOR_DEPTH");
-        if (seg[7] != 0) return bad("reserved word is not zero");
         if (base != need.alphas) return bad("a segment's alpha base is not the sum of the terms before it");
+        if (seg_kind) seg_kind[s] = seg[7];
+        if (seg[7] != 0) {
+            if (const int rc = check_native(seg, need)) return rc;
+            need.alphas += terms;
+            if (seg_offset) seg_offset[s] = at;
+            continue;
+        }
         const uint64_t* desc = seg + GT_HDR;
         const uint64_t* instr = desc + G * GT_DESC;
         const uint64_t* writes = instr + I;
@@ -428,11 +475,18 @@ extern "C" {
 
 int bj_gate_set_check_h(const uint64_t* image, size_t words, uint64_t* need) {
     bj::Need n;
-    if (const int rc = bj::check_image(image, words, n, nullptr)) return rc;
+    if (const int rc = bj::check_image(image, words, n, nullptr, nullptr)) return rc;
     if (need) {
         need[0] = n.cols[0], need[1] = n.cols[1], need[2] = n.cols[2];
         need[3] = n.alphas, need[4] = n.segments;
     }
+    return BJ_OK;
+}
+
+int bj_gate_native_info_h(uint32_t kind, uint64_t* out) {
+    if (kind != bj::p2g::KIND) return bj::set_error(BJ_EINVAL, "bj_gate_native_info_h: unknown native gate kind");
+    if (!out) return bj::set_error(BJ_EINVAL, "bj_gate_native_info_h: null out");
+    out[0] = bj::p2g::CELLS, out[1] = bj::p2g::TERMS, out[2] = bj::p2g::DEGREE, out[3] = bj::p2g::MAX_WITNESS_CELLS;
     return BJ_OK;
 }
 
@@ -441,7 +495,7 @@ int bj_gate_set_upload_d(const uint64_t* image, size_t words, void** set) {
     *set = nullptr;
     bj::GateSet* s = new (std::nothrow) bj::GateSet;
     if (!s) return bj::set_error(BJ_EINVAL, "bj_gate_set_upload_d: out of host memory");
-    if (const int rc = bj::check_image(image, words, s->need, s->seg_offset)) {
+    if (const int rc = bj::check_image(image, words, s->need, s->seg_offset, s->seg_kind)) {
         delete s;
         return rc;
     }
@@ -488,8 +542,9 @@ int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* 
         return rc;
     if (s->need.alphas > n_alphas) return bj::set_error(BJ_EINVAL, "gate program: fewer challenges than terms");
     const size_t blocks = (total + bj::GT_THREADS - 1) / bj::GT_THREADS;
-    hipLaunchKernelGGL(bj::gate_terms_kernel, dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, bj::S(stream),
-                       s->image_d + s->seg_offset[segment], cols, alphas, total, dst0, dst1);
+    hipLaunchKernelGGL(s->seg_kind[segment] ? bj::p2g::gate_terms_kernel : bj::gate_terms_kernel, dim3((unsigned)blocks),
+                       dim3(bj::GT_THREADS), 0, bj::S(stream), s->image_d + s->seg_offset[segment], cols, alphas, total,
+                       dst0, dst1);
     return bj::ok_or(hipGetLastError(), "quotient gate terms");
 }
 
@@ -518,10 +573,11 @@ int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* v
     const uint64_t* seg = s->image_d + s->seg_offset[segment];
     if (begin) hipLaunchKernelGGL(bj::gate_check_begin_kernel, dim3(1), dim3(bj::GC_WAVE), 0, st, status);
     const size_t blocks = (size_t)((n_rows + bj::GT_THREADS - 1) / bj::GT_THREADS);
-    hipLaunchKernelGGL(bj::gate_check_kernel<false>, dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, st, seg, cols,
-                       row_begin, n_rows, status);
-    hipLaunchKernelGGL(bj::gate_check_kernel<true>, dim3(1), dim3(bj::GC_WAVE), 0, st, seg, cols, row_begin, n_rows,
-                       status);
+    const bool native = s->seg_kind[segment] != 0;
+    hipLaunchKernelGGL(native ? bj::p2g::gate_check_kernel<false> : bj::gate_check_kernel<false>, dim3((unsigned)blocks),
+                       dim3(bj::GT_THREADS), 0, st, seg, cols, row_begin, n_rows, status);
+    hipLaunchKernelGGL(native ? bj::p2g::gate_check_kernel<true> : bj::gate_check_kernel<true>, dim3(1),
+                       dim3(bj::GC_WAVE), 0, st, seg, cols, row_begin, n_rows, status);
     return bj::ok_or(hipGetLastError(), "gate set satisfiability check");
 }
 

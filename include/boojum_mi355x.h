@@ -706,12 +706,13 @@ int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out);
  * The image (u64 words; INTEGRATION.md "Gate programs" describes how to build one from a capture):
  *   [0] 0x3153455441474A42 ("BJGATES1")  [1] segments S  [2 .. 2 + S) word offset of each segment
  *   segment:    [0] gates G  [1] instructions I  [2] writes W  [3] immediates M  [4] alpha base (the
- *               terms of the segments before it)  [5] terms  [6] deepest selector path  [7] 0, then
+ *               terms of the segments before it)  [5] terms  [6] deepest selector path  [7] kind:
+ *               0 interpreted, 1 native Poseidon2 flattened gate (below), then
  *               G descriptors of 8 words, I instructions, W writes, M immediates
  *   descriptor: [0] instruction begin | end << 32  [1] write begin | end << 32 (in push order)
  *               [2] num_repetitions | path length << 32  [3] path mask, bit i set: column i, clear:
  *               1 - column i  [4] variables base | per repetition << 32  [5] witnesses, [6]
- *               constants likewise  [7] 0
+ *               constants likewise  [7] 0 (native segment: num_witness_columns_used)
  *   instruction: opcode | destination slot << 8 | operand a << 16 | operand b << 40
  *   operand (24 bits): kind << 21 | index; kinds 0 VariablePoly, 1 WitnessPoly, 2 ConstantPoly,
  *               3 slot, 4 immediate (index into the segment's M words); a write is one operand
@@ -722,6 +723,20 @@ int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out);
  * BJ_GATE_MAX_GATES gates and BJ_GATE_MAX_INSTRUCTIONS instructions (and as many writes and
  * immediates); a larger set is several segments and several calls, which is exact because every
  * call adds to dst.
+ *
+ * Native segments.  A gate whose capture passes the caps of a launch whatever the split --
+ * Poseidon2RoundFunctionFlattenedEvaluator<F, 8, 12, 4> over Goldilocks (cs/gates/poseidon2.rs:166-403)
+ * is about 31 matrix layers of 144 relations with more than BJ_GATE_MAX_SLOTS values live -- goes in a
+ * segment of its own with a kind other than 0 in word [7], and the two calls below run a written-out
+ * kernel on it instead of the interpreter, with the same arguments and the same contract.  Kind 1 is
+ * that gate: 130 cells, 118 terms in the reference's push order (36 + 22 + 48 resets, then output -
+ * state), degree 7.  Such a segment has G = 1 and I = W = M = 0; its descriptor's [0] is 0, [1] is
+ * 0 | 118 << 32 with no writes behind it (so the terms of a gate are read from a descriptor alike for
+ * both kinds), [2] .. [6] keep their meaning and [7] is nw = num_witness_columns_used <= 106: S-box
+ * output cell s reads witness column s while s < nw and variable column 24 + s - nw after that,
+ * variables 0 .. 11 being the input and 12 .. 23 the output.  Variables per repetition must be at
+ * least 130 - nw and witnesses per repetition at least nw; terms = 118 * repetitions.  The magic is
+ * unchanged, and an image without native segments is word for word what it was.
  *
  * Checks, all on the host and none per point: the magic, every range, the caps, an operand outside
  * its space, a slot read before it is written in its gate, a term count or alpha base that does
@@ -738,6 +753,12 @@ int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out);
  * witness and constant columns the largest repetition reaches (the selector columns included), the
  * challenges the whole image consumes, the segments.  BJ_EINVAL as listed above. */
 int bj_gate_set_check_h(const uint64_t* image, size_t words, uint64_t* need);
+
+/* What a native segment kind is, for a caller that builds images: out[0] the cells of one repetition
+ * (130), [1] its terms (118), [2] the constraint degree (7), [3] the most cells that may be witness
+ * columns (106).  Added after 2.6; detect by symbol (bj_abi_version() is unchanged): a library
+ * without it refuses word [7] != 0.  Host only.  BJ_EINVAL: an unknown kind, null out. */
+int bj_gate_native_info_h(uint32_t kind, uint64_t* out);
 
 /* bj_gate_set_check_h, then the one upload: allocates words * 8 bytes on the current device, copies
  * the image and synchronises.  *set is the handle the evaluation takes; it keeps the device buffer
