@@ -385,6 +385,15 @@ class _Segment:
         return head + self.desc + self.instr + self.writes + self.imm
 
 
+def _placement_words(pl):
+    """Words [2] .. [6] of a descriptor: repetitions | path length << 32, the path's mask, three base | per << 32."""
+    path = pl.selector_path
+    if len(path) > 63:
+        raise ValueError("selector path too long")
+    return [pl.num_repetitions | len(path) << 32, sum(1 << i for i, b in enumerate(path) if b)] + \
+        [base | per << 32 for base, per in zip(pl.bases(), pl.per_chunk_offset.as_tuple())]
+
+
 def _encode_gate(seg, pl, cap):
     """Appends one gate to a segment; returns False (segment untouched) when it does not fit."""
     prog = pl.program
@@ -413,14 +422,8 @@ def _encode_gate(seg, pl, cap):
     if (len(seg.desc) // 8 + 1 > MAX_GATES or len(seg.instr) + len(instr) > MAX_INSTRUCTIONS
             or len(seg.writes) + len(writes) > MAX_INSTRUCTIONS or len(imm) > MAX_INSTRUCTIONS):
         return False
-    if len(pl.selector_path) > 63:
-        raise ValueError("selector path too long")
-    mask = sum(1 << i for i, b in enumerate(pl.selector_path) if b)
-    bases, per = pl.bases(), pl.per_chunk_offset.as_tuple()
     i0, w0 = len(seg.instr), len(seg.writes)
-    seg.desc += [i0 | (i0 + len(instr)) << 32, w0 | (w0 + len(writes)) << 32,
-                 pl.num_repetitions | len(pl.selector_path) << 32, mask,
-                 bases[0] | per[0] << 32, bases[1] | per[1] << 32, bases[2] | per[2] << 32, 0]
+    seg.desc += [i0 | (i0 + len(instr)) << 32, w0 | (w0 + len(writes)) << 32] + _placement_words(pl) + [0]
     seg.instr += instr
     seg.writes += writes
     seg.imm, seg.imm_index = imm, imm_index
@@ -443,17 +446,13 @@ def _encode_native(seg, pl, kind):
     cells, terms, _, most_witnesses = info
     evaluator = pl.program.evaluator
     nw = evaluator.num_witness_columns_used
-    bases, per = pl.bases(), pl.per_chunk_offset.as_tuple()
+    per = pl.per_chunk_offset.as_tuple()
     if terms != evaluator.num_quotient_terms or not 0 <= nw <= most_witnesses:
         raise ValueError("%s does not match the library's native kind %d" % (evaluator.name, kind))
     if per[0] < cells - nw or per[1] < nw:
         raise ValueError("a repetition of %s is narrower than its %d cells" % (evaluator.name, cells))
-    if len(pl.selector_path) > 63:
-        raise ValueError("selector path too long")
-    mask = sum(1 << i for i, b in enumerate(pl.selector_path) if b)
+    seg.desc += [0, terms << 32] + _placement_words(pl) + [nw]
     seg.kind = kind
-    seg.desc += [0, terms << 32, pl.num_repetitions | len(pl.selector_path) << 32, mask,
-                 bases[0] | per[0] << 32, bases[1] | per[1] << 32, bases[2] | per[2] << 32, nw]
     seg.terms = pl.num_terms()
     seg.depth = len(pl.selector_path)
 
@@ -468,26 +467,26 @@ def compile_gate_set(placements, slot_cap=MAX_SLOTS):
     if not placements:
         raise ValueError("a gate set holds at least one gate with quotient terms")
     segments, seg = [], _Segment(0)
+
+    def close():   # a segment that holds a gate is done; the next one carries the challenge index on
+        nonlocal seg
+        if seg.desc:
+            segments.append(seg)
+            seg = _Segment(seg.alpha_base + seg.terms)
+
     for pl in placements:
         if pl.program.num_quotient_terms == 0:
             raise ValueError("a gate without quotient terms never reaches the library (prover.rs:922-994)")
         if _native_kind(pl):
-            if seg.desc:
-                segments.append(seg)
-                seg = _Segment(seg.alpha_base + seg.terms)
+            close()
             _encode_native(seg, pl, _native_kind(pl))
-            segments.append(seg)
-            seg = _Segment(seg.alpha_base + seg.terms)
-            continue
-        if not _encode_gate(seg, pl, slot_cap):
-            if not seg.desc:
+            close()
+        elif not _encode_gate(seg, pl, slot_cap):
+            empty = not seg.desc   # an empty segment did not take the gate: none will
+            close()
+            if empty or not _encode_gate(seg, pl, slot_cap):
                 raise ValueError("one gate exceeds the caps of a launch")
-            segments.append(seg)
-            seg = _Segment(seg.alpha_base + seg.terms)
-            if not _encode_gate(seg, pl, slot_cap):
-                raise ValueError("one gate exceeds the caps of a launch")
-    if seg.desc:
-        segments.append(seg)
+    close()
     image = [MAGIC, len(segments)] + [0] * len(segments)
     for i, s in enumerate(segments):
         image[2 + i] = len(image)
@@ -594,20 +593,42 @@ class GateSet:
             pass
 
 
-def _lde(t, q, what):
-    """(data pointer, column stride, columns, n) of a (C, D, n) LDE, or zeros for None."""
-    if t is None:
-        return None, 0, 0, None
+def _view(t, what, rank, shape):
+    """t.shape, after the check behind _lde and _trace: u64 words on the device in `rank` dimensions."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.int64, torch.uint64):
         raise TypeError("%s: expected an int64 CUDA tensor of u64 field elements" % what)
-    if t.dim() != 3:
-        raise ValueError("%s: an LDE is (C, D, n)" % what)
-    c, d, n = t.shape
+    if t.dim() != rank:
+        raise ValueError("%s: %s" % (what, shape))
+    return t.shape
+
+
+def _lde(t, q, what):
+    """(data pointer, column stride, columns, n) of a (C, D, n) LDE."""
+    c, d, n = _view(t, what, 3, "an LDE is (C, D, n)")
     if d < q:
         raise ValueError("%s: the LDE has %d cosets, the quotient degree is %d" % (what, d, q))
     if t.stride(2) != 1 or (d > 1 and t.stride(1) != n):
         raise ValueError("%s: the cosets of an LDE column must be contiguous" % what)
     return t.data_ptr(), (t.stride(0) if c > 1 else d * n), c, n
+
+
+def _trace(t, what):
+    """(data pointer, column stride, columns, n) of (C, n) trace columns."""
+    c, n = _view(t, what, 2, "trace columns are (C, n)")
+    if n and t.stride(1) != 1:
+        raise ValueError("%s: the rows of a trace column must be contiguous" % what)
+    return t.data_ptr(), (t.stride(0) if c > 1 else n), c, n
+
+
+def _bind(view, **tensors):
+    """The variables, witnesses and constants of a call, each through `view` (_lde or _trace) under its argument's
+    name, None for a kind the set never names: the nine column arguments of the C calls and the set of row counts."""
+    args, sizes = [], set()
+    for what, t in tensors.items():
+        p, stride, c, n = (None, 0, 0, None) if t is None else view(t, what)
+        args += [p, stride, c]
+        sizes.add(n)
+    return args, sizes - {None}
 
 
 def challenges_tensor(alphas, device):
@@ -624,10 +645,8 @@ def evaluate_gate_terms(gate_set, variables_lde, witnesses_lde, constants_lde, a
     (c0, c1) pairs (copied to the device here) or a (K, 2) device tensor (read in place, so a
     captured graph sees later contents).  dst_c0, dst_c1: q * n words each."""
     log_q = log2_exact(quotient_degree)
-    v, v_stride, n_v, n1 = _lde(variables_lde, quotient_degree, "variables_lde")
-    w, w_stride, n_w, n2 = _lde(witnesses_lde, quotient_degree, "witnesses_lde")
-    c, c_stride, n_c, n3 = _lde(constants_lde, quotient_degree, "constants_lde")
-    sizes = {n for n in (n1, n2, n3) if n is not None}
+    columns, sizes = _bind(lambda t, what: _lde(t, quotient_degree, what), variables_lde=variables_lde,
+                           witnesses_lde=witnesses_lde, constants_lde=constants_lde)
     total = dst_c0.numel()
     n = sizes.pop() if sizes else total // quotient_degree
     if sizes or n * quotient_degree != total:
@@ -641,9 +660,8 @@ def evaluate_gate_terms(gate_set, variables_lde, witnesses_lde, constants_lde, a
             or alphas.dtype not in (torch.int64, torch.uint64):
         raise ValueError("alphas: a contiguous (K, 2) int64 device tensor")
     for segment in range(gate_set.num_segments):
-        call("bj_quotient_gate_terms_d", gate_set._handle, segment, v, v_stride, n_v, w, w_stride, n_w, c, c_stride,
-             n_c, alphas.data_ptr(), alphas.shape[0], log2_exact(n), log_q, dst_c0.data_ptr(), dst_c1.data_ptr(),
-             stream_of(dst_c0))
+        call("bj_quotient_gate_terms_d", gate_set._handle, segment, *columns, alphas.data_ptr(), alphas.shape[0],
+             log2_exact(n), log_q, dst_c0.data_ptr(), dst_c1.data_ptr(), stream_of(dst_c0))
 
 
 # ------------------------------------------------------------------ satisfiability check
@@ -693,20 +711,6 @@ def report_from_status(gate_set, status):
     return SatisfiabilityReport(count, row, gate, gate_set.gate_name(gate), subinstance, term, k, value)
 
 
-def _trace(t, what):
-    """(data pointer, column stride, columns, n) of (C, n) trace columns, or zeros for None."""
-    if t is None:
-        return None, 0, 0, None
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.int64, torch.uint64):
-        raise TypeError("%s: expected an int64 CUDA tensor of u64 field elements" % what)
-    if t.dim() != 2:
-        raise ValueError("%s: trace columns are (C, n)" % what)
-    c, n = t.shape
-    if n and t.stride(1) != 1:
-        raise ValueError("%s: the rows of a trace column must be contiguous" % what)
-    return t.data_ptr(), (t.stride(0) if c > 1 else n), c, n
-
-
 def check_if_satisfied(gate_set, variables, witnesses, constants, rows=None, status=None):
     """CSReferenceAssembly::check_if_satisfied (satisfiability_test.rs:15-353) on the device: every
     gate of gate_set on every row of the window, over the (C, n) trace columns the commitment takes
@@ -714,10 +718,7 @@ def check_if_satisfied(gate_set, variables, witnesses, constants, rows=None, sta
     whole trace.  One bj_gate_set_satisfied_d call per segment on one status record (`status`: a
     4-word int64 device tensor to use for it), then one copy of its 4 words to the host, which
     synchronises.  Returns a SatisfiabilityReport."""
-    v, v_stride, n_v, n1 = _trace(variables, "variables")
-    w, w_stride, n_w, n2 = _trace(witnesses, "witnesses")
-    c, c_stride, n_c, n3 = _trace(constants, "constants")
-    sizes = {n for n in (n1, n2, n3) if n is not None}
+    columns, sizes = _bind(_trace, variables=variables, witnesses=witnesses, constants=constants)
     if len(sizes) != 1:
         raise ValueError("the trace columns disagree on the number of rows" if sizes else "no trace columns")
     n = sizes.pop()
@@ -731,8 +732,8 @@ def check_if_satisfied(gate_set, variables, witnesses, constants, rows=None, sta
             or not status.is_contiguous():
         raise ValueError("status: 4 contiguous int64 words on the device")
     for segment in range(gate_set.num_segments):
-        call("bj_gate_set_satisfied_d", gate_set._handle, segment | (CHECK_BEGIN if segment == 0 else 0), v, v_stride,
-             n_v, w, w_stride, n_w, c, c_stride, n_c, begin, count, status.data_ptr(), stream_of(first))
+        call("bj_gate_set_satisfied_d", gate_set._handle, segment | (CHECK_BEGIN if segment == 0 else 0), *columns,
+             begin, count, status.data_ptr(), stream_of(first))
     return report_from_status(gate_set, read_status(status))
 
 

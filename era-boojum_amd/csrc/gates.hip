@@ -12,16 +12,20 @@
 // (cs/traits/evaluator.rs:376-397), compute_selector_subpath (prover.rs:2775-2916) and the
 // specialized-columns form, which has no selector (prover.rs:651-801).
 //
-// Kernel.  One point per lane, 256 lanes per workgroup, one launch for all gates of a segment; the
-// accumulator is read once and written once.  The program is wave-uniform: every word of it is
-// fetched through a uniform address of the uploaded image and forced into scalar registers
-// (readfirstlane), so the decode (field extracts, the operand-kind and opcode branches, the
-// column-address arithmetic) is scalar work and no lane takes a branch another does not.  A
-// temporary lives in an LDS slot laid out [slot][lane], 8 bytes per lane, so a wave's access is
-// 512 contiguous bytes: conflict free by construction, private to the lane, and no barrier is
-// needed.  The host allocates slots by liveness (boojum_amd/gates.py), so GT_SLOTS bounds the
-// values live at once, not the program's length.  The selector constants of a point (columns
-// 0 .. depth - 1) are loaded once into registers and every gate multiplies its own path from them.
+// Structure.  Three frames, one per launch (gate_terms_kernel, gate_check_kernel, gate_value_kernel),
+// each instantiated per program kind, whose walk hands the terms of one repetition of one gate to a
+// sink.  Placement, the selector product and the three sinks are written once for all of them.  One
+// point per lane, 256 lanes per workgroup, one launch for all gates of a segment.
+//
+// Kind 0, the Interpreter.  The program is wave-uniform: every word of it is fetched through a
+// uniform address of the uploaded image and forced into scalar registers (readfirstlane), so the
+// decode (field extracts, the operand-kind and opcode branches, the column-address arithmetic) is
+// scalar work and no lane takes a branch another does not.  A temporary lives in an LDS slot laid
+// out [slot][lane], 8 bytes per lane, so a wave's access is 512 contiguous bytes: conflict free by
+// construction, private to the lane, and no barrier is needed.  The host allocates slots by
+// liveness (boojum_amd/gates.py), so GT_SLOTS bounds the values live at once, not the program's
+// length.  The selector constants of a point (columns 0 .. depth - 1) are loaded once into
+// registers and every gate multiplies its own path from them.
 //
 // Image (u64 words, built by the caller, checked by check_image below, uploaded once):
 //   [0] GT_MAGIC  [1] number of segments S  [2 .. 2 + S) word offset of each segment
@@ -41,15 +45,16 @@
 //   (fma_gate_without_constant.rs:353, fma_gate_in_extension_without_constant.rs:451,
 //   zero_check.rs:539) are all inside witness-resolution closures, not evaluate_once.
 //
-// A native segment holds one gate of a kind the library has a written-out kernel for: G = 1,
-// I = W = M = 0, the descriptor's [0] is 0 and its [1] is 0 | terms per repetition << 32 with no
-// writes behind it, [2] .. [6] keep their meaning.  The two entry points dispatch on the kind.
+// A native segment holds one gate of a kind whose walk is written out (kind 1, p2g::Program, no LDS):
+// G = 1, I = W = M = 0, the descriptor's [0] is 0 and its [1] is 0 | terms per repetition << 32 with
+// no writes behind it, [2] .. [6] keep their meaning.  The two entry points pick the frame's
+// instantiation by the kind.
 //
 // One call launches one segment.  A gate set over the caps is split into segments by the caller,
 // which is exact because the call adds to the accumulator and a segment carries its alpha base.
 //
 // The same image also answers where a witness fails its gates (check_if_satisfied,
-// cs/implementations/satisfiability_test.rs:15-353): gate_check_kernel below walks the programs over
+// cs/implementations/satisfiability_test.rs:15-353): gate_check_kernel walks the same programs over
 // trace rows and reports the count and the first failing (row, term) in a status record.
 #include <hip/hip_runtime.h>
 #include <new>
@@ -86,89 +91,214 @@ __device__ __forceinline__ uint64_t uword(const uint64_t* __restrict__ p) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-__device__ __forceinline__ uint64_t fetch(uint32_t operand, const Cols& cols, const uint32_t (&off)[3], size_t L,
-                                          const uint64_t* slots, const uint64_t* __restrict__ imm) {
-    const uint32_t kind = operand >> IDX_BITS, idx = operand & IDX_MASK;
-    if (kind == K_SLOT) return slots[idx * GT_THREADS];
-    if (kind == K_IMM) return uword(imm + idx);
-    if (kind == K_VAR) return cols.p[0][(size_t)(idx + off[0]) * cols.stride[0] + L];
-    if (kind == K_WIT) return cols.p[1][(size_t)(idx + off[1]) * cols.stride[1] + L];
-    return cols.p[2][(size_t)(idx + off[2]) * cols.stride[2] + L];
+// Where a gate sits: words [2] .. [7] of its descriptor, decoded once into scalar registers.
+struct Placement {
+    uint32_t reps, depth, base[3], per[3], word7;
+    uint64_t mask;
+
+    __device__ __forceinline__ explicit Placement(const uint64_t* __restrict__ d) {
+        const uint64_t d2 = uword(d + 2);
+        reps = (uint32_t)d2, depth = (uint32_t)(d2 >> 32), mask = uword(d + 3);
+#pragma unroll
+        for (uint32_t k = 0; k < 3; k++) {
+            const uint64_t w = uword(d + 4 + k);
+            base[k] = (uint32_t)w, per[k] = (uint32_t)(w >> 32);
+        }
+        word7 = (uint32_t)uword(d + 7);
+    }
+};
+
+// The path product over constant columns 0 .. depth - 1: column i, or 1 - column i where the mask's
+// bit i is clear; 1 for an empty path.  The program kind gives the column values and says how far to unroll.
+template <class Program>
+__device__ __forceinline__ uint64_t selector(const Placement& pl, const Program& prog) {
+    uint64_t sel = 1;
+#pragma unroll Program::SELECTOR_UNROLL
+    for (uint32_t i = 0; i < GT_SEL && i < pl.depth; i++) {
+        const uint64_t c = prog.selector_column(i);
+        const uint64_t f = (pl.mask >> i) & 1 ? c : gl::sub(1, c);
+        sel = i == 0 ? f : gl::mul(sel, f);
+    }
+    return sel;
 }
 
+// ------------------------------------------------------------------ what happens to a term
+// A walk hands every term to sink.emit(v) in push order; the frame around it sets what changes per gate
+// and stops walking once the sink is done().
+
+// g += alpha[k] term, two base products, k running on from the segment's alpha base
+struct AccumulatorSink {
+    const uint64_t* __restrict__ alpha;
+    uint64_t g0, g1;
+    __device__ __forceinline__ void emit(uint64_t v) {
+        g0 = gl::add(g0, gl::mul(v, uword(alpha)));
+        g1 = gl::add(g1, gl::mul(v, uword(alpha + 1)));
+        alpha += 2;
+    }
+    __device__ __forceinline__ bool done() const { return false; }
+};
+
+// the lane's failing terms (selector * term != 0): their number and the first k, the smallest as k only grows
+struct CheckSink {
+    uint64_t sel, count;
+    uint32_t k, first;
+    bool selected, in;
+    __device__ __forceinline__ void emit(uint64_t v) {
+        const bool fail = in && gl::canon(selected ? gl::mul(v, sel) : v) != 0;
+        first = fail && count == 0 ? k : first;
+        count += fail;
+        k++;
+    }
+    __device__ __forceinline__ bool done() const { return false; }
+};
+
+// the canonical value of term `target` to the record (wave-uniform: every lane walks the same row)
+struct ValueSink {
+    unsigned long long* __restrict__ status;
+    uint32_t k, target;
+    __device__ __forceinline__ void emit(uint64_t v) {
+        if (k == target && threadIdx.x == 0) status[2] = gl::canon(v);
+        k++;
+    }
+    __device__ __forceinline__ bool done() const { return k > target; }
+};
+
+// ------------------------------------------------------------------ the program kinds
+// A kind says how many LDS slots a lane needs (SLOTS) and is made per lane for (segment, columns,
+// point L, the lane's slots).  It gives the frames gate(d) at each descriptor, walk(placement, off,
+// sink) for one repetition of that gate at L and the repetition's three column offsets, and the point's
+// selector columns (read_selector_columns() once where a frame forms selectors, then selector_column(i)).
+#include "gates_poseidon2.hpp"
+
+// Kind 0: the relation programs of the image, temporaries in this lane's column of the LDS slots.
+struct Interpreter {
+    static constexpr uint32_t SELECTOR_UNROLL = GT_SEL;  // the columns are registers: static indices
+    static constexpr uint32_t GATES = 0;                 // as many as the segment says
+    static constexpr uint32_t SLOTS = GT_SLOTS;
+    const Cols& cols;
+    const size_t L;
+    uint64_t* slots;
+    const uint64_t* __restrict__ instr;
+    const uint64_t* __restrict__ writes;
+    const uint64_t* __restrict__ imm;
+    uint32_t i0, i1, w0, w1;  // the current gate's instruction and write ranges
+    uint32_t sel_cols;        // selector columns the segment reads
+    uint64_t selc[GT_SEL];    // their values at the point, loaded once for all gates
+
+    __device__ __forceinline__ Interpreter(const uint64_t* __restrict__ seg, const Cols& cols, size_t L, uint64_t* slots)
+        : cols(cols), L(L), slots(slots) {
+        instr = seg + GT_HDR + (size_t)(uint32_t)uword(seg + 0) * GT_DESC;
+        writes = instr + (uint32_t)uword(seg + 1);
+        imm = writes + (uint32_t)uword(seg + 2);
+        sel_cols = (uint32_t)uword(seg + 6);
+    }
+    __device__ __forceinline__ void read_selector_columns() {
+#pragma unroll
+        for (uint32_t i = 0; i < GT_SEL; i++) selc[i] = i < sel_cols ? cols.p[2][(size_t)i * cols.stride[2] + L] : 0;
+    }
+    __device__ __forceinline__ void gate(const uint64_t* __restrict__ d) {
+        const uint64_t d0 = uword(d), d1 = uword(d + 1);
+        i0 = (uint32_t)d0, i1 = (uint32_t)(d0 >> 32), w0 = (uint32_t)d1, w1 = (uint32_t)(d1 >> 32);
+    }
+    __device__ __forceinline__ uint64_t selector_column(uint32_t i) const { return selc[i]; }
+
+    __device__ __forceinline__ uint64_t fetch(uint32_t operand, const uint32_t (&off)[3]) const {
+        const uint32_t kind = operand >> IDX_BITS, idx = operand & IDX_MASK;
+        if (kind == K_SLOT) return slots[idx * GT_THREADS];
+        if (kind == K_IMM) return uword(imm + idx);
+        if (kind == K_VAR) return cols.p[0][(size_t)(idx + off[0]) * cols.stride[0] + L];
+        if (kind == K_WIT) return cols.p[1][(size_t)(idx + off[1]) * cols.stride[1] + L];
+        return cols.p[2][(size_t)(idx + off[2]) * cols.stride[2] + L];
+    }
+    template <class Sink>
+    __device__ __forceinline__ void walk(const Placement&, const uint32_t (&off)[3], Sink& sink) const {
+        for (uint32_t pc = i0; pc < i1; pc++) {
+            const uint64_t w = uword(instr + pc);
+            const uint32_t op = (uint32_t)w & 0xff, slot = (uint32_t)(w >> 8) & 0xff;
+            const uint64_t a = fetch((uint32_t)(w >> 16) & 0xffffff, off);
+            uint64_t r;
+            if (op == OP_DOUBLE) {
+                r = gl::add(a, a);
+            } else if (op == OP_NEGATE) {
+                r = gl::sub(0, a);
+            } else if (op == OP_SQUARE) {
+                r = gl::mul(a, a);
+            } else {
+                const uint64_t b = fetch((uint32_t)(w >> 40) & 0xffffff, off);
+                r = op == OP_MUL ? gl::mul(a, b) : op == OP_ADD ? gl::add(a, b) : gl::sub(a, b);
+            }
+            slots[slot * GT_THREADS] = r;
+        }
+        for (uint32_t t = w0; t < w1; t++) sink.emit(fetch((uint32_t)uword(writes + t) & 0xffffff, off));
+    }
+};
+
+// ------------------------------------------------------------------ the frames
+// A frame owns the LDS slots, the lane's point and its guard, the gate loop, what the sink needs per
+// gate, and what leaves the kernel.
+
+// This lane's column of the [slot][lane] LDS slots, if the kind asks for any.
+template <class Program>
+__device__ __forceinline__ uint64_t* lane_slots() {
+    if constexpr (Program::SLOTS != 0) {
+        __shared__ uint64_t lds[Program::SLOTS * GT_THREADS];
+        return lds + threadIdx.x;
+    }
+    return nullptr;
+}
+
+// The repetitions of one gate, the column offsets running on by the placement's per-repetition steps.
+template <class Program, class Sink>
+__device__ __forceinline__ void repetitions(const Program& prog, const Placement& pl, Sink& sink) {
+    uint32_t off[3] = {pl.base[0], pl.base[1], pl.base[2]};
+    for (uint32_t rep = 0; rep < pl.reps && !sink.done(); rep++) {
+        prog.walk(pl, off, sink);
+#pragma unroll
+        for (uint32_t k = 0; k < 3; k++) off[k] += pl.per[k];
+    }
+}
+
+// The gates of a segment: word [0], or what the kind fixes (the validator holds a native segment to it).
+template <class Program>
+__device__ __forceinline__ uint32_t gates_of(const uint64_t* __restrict__ seg) {
+    return Program::GATES ? Program::GATES : (uint32_t)uword(seg + 0);
+}
+
+// Lane l of a launch over `count` points from `first`.  A lane past the end walks the first point, so
+// its loads stay in bounds, and (`in` false) writes and counts nothing.
+__device__ __forceinline__ size_t lane_point(uint64_t first, uint64_t count, bool& in) {
+    const size_t l = blockIdx.x * (size_t)GT_THREADS + threadIdx.x;
+    in = l < count;
+    return (size_t)first + (in ? l : 0);
+}
+
+// bj_quotient_gate_terms_d: acc(L) += sum_gates selector_g(L) sum_rep sum_term alpha[k] term(L); the
+// selector multiplies a gate's sum once, the accumulator is read once and written once.
+template <class Program>
 __global__ __launch_bounds__(GT_THREADS) void gate_terms_kernel(const uint64_t* __restrict__ seg, Cols cols,
                                                                 const uint64_t* __restrict__ alphas, size_t total,
                                                                 uint64_t* __restrict__ dst0,
                                                                 uint64_t* __restrict__ dst1) {
-    __shared__ uint64_t lds[GT_SLOTS * GT_THREADS];
-    uint64_t* slots = lds + threadIdx.x;
-    const size_t l = blockIdx.x * (size_t)GT_THREADS + threadIdx.x;
-    const bool in = l < total;
-    const size_t L = in ? l : 0;  // a lane past the end reads point 0 and writes nothing
-
-    const uint32_t n_gates = (uint32_t)uword(seg + 0), n_instr = (uint32_t)uword(seg + 1);
-    const uint32_t n_writes = (uint32_t)uword(seg + 2), sel_cols = (uint32_t)uword(seg + 6);
-    const uint64_t* __restrict__ desc = seg + GT_HDR;
-    const uint64_t* __restrict__ instr = desc + (size_t)n_gates * GT_DESC;
-    const uint64_t* __restrict__ writes = instr + n_instr;
-    const uint64_t* __restrict__ imm = writes + n_writes;
-    const uint64_t* __restrict__ alpha = alphas + 2 * uword(seg + 4);
-
-    uint64_t selc[GT_SEL];
-#pragma unroll
-    for (uint32_t i = 0; i < GT_SEL; i++) selc[i] = i < sel_cols ? cols.p[2][(size_t)i * cols.stride[2] + L] : 0;
-
+    bool in;
+    const size_t L = lane_point(0, total, in);
+    Program prog(seg, cols, L, lane_slots<Program>());
+    prog.read_selector_columns();
+    AccumulatorSink sink{alphas + 2 * uword(seg + 4), 0, 0};
     uint64_t acc0 = 0, acc1 = 0;
+    const uint32_t n_gates = gates_of<Program>(seg);
     for (uint32_t g = 0; g < n_gates; g++) {
-        const uint64_t* __restrict__ d = desc + (size_t)g * GT_DESC;
-        const uint64_t d0 = uword(d), d1 = uword(d + 1), d2 = uword(d + 2), mask = uword(d + 3);
-        const uint64_t dv = uword(d + 4), dw = uword(d + 5), dc = uword(d + 6);
-        const uint32_t i0 = (uint32_t)d0, i1 = (uint32_t)(d0 >> 32), w0 = (uint32_t)d1, w1 = (uint32_t)(d1 >> 32);
-        const uint32_t reps = (uint32_t)d2, depth = (uint32_t)(d2 >> 32);
-        uint32_t off[3] = {(uint32_t)dv, (uint32_t)dw, (uint32_t)dc};
-        uint64_t g0 = 0, g1 = 0;
-        for (uint32_t rep = 0; rep < reps; rep++) {
-            for (uint32_t pc = i0; pc < i1; pc++) {
-                const uint64_t w = uword(instr + pc);
-                const uint32_t op = (uint32_t)w & 0xff, slot = (uint32_t)(w >> 8) & 0xff;
-                const uint64_t a = fetch((uint32_t)(w >> 16) & 0xffffff, cols, off, L, slots, imm);
-                uint64_t r;
-                if (op == OP_DOUBLE) {
-                    r = gl::add(a, a);
-                } else if (op == OP_NEGATE) {
-                    r = gl::sub(0, a);
-                } else if (op == OP_SQUARE) {
-                    r = gl::mul(a, a);
-                } else {
-                    const uint64_t b = fetch((uint32_t)(w >> 40) & 0xffffff, cols, off, L, slots, imm);
-                    r = op == OP_MUL ? gl::mul(a, b) : op == OP_ADD ? gl::add(a, b) : gl::sub(a, b);
-                }
-                slots[slot * GT_THREADS] = r;
-            }
-            for (uint32_t t = w0; t < w1; t++) {  // alpha_k * term: two base products
-                const uint64_t v = fetch((uint32_t)uword(writes + t) & 0xffffff, cols, off, L, slots, imm);
-                g0 = gl::add(g0, gl::mul(v, uword(alpha)));
-                g1 = gl::add(g1, gl::mul(v, uword(alpha + 1)));
-                alpha += 2;
-            }
-            off[0] += (uint32_t)(dv >> 32);
-            off[1] += (uint32_t)(dw >> 32);
-            off[2] += (uint32_t)(dc >> 32);
+        const uint64_t* __restrict__ d = seg + GT_HDR + (size_t)g * GT_DESC;
+        const Placement pl(d);
+        prog.gate(d);
+        sink.g0 = sink.g1 = 0;
+        repetitions(prog, pl, sink);
+        if (pl.depth) {
+            const uint64_t sel = selector(pl, prog);
+            sink.g0 = gl::mul(sink.g0, sel);
+            sink.g1 = gl::mul(sink.g1, sel);
         }
-        if (depth) {  // the selector multiplies the gate's sum once
-            uint64_t sel = 1;
-#pragma unroll
-            for (uint32_t i = 0; i < GT_SEL; i++) {
-                if (i < depth) {
-                    const uint64_t f = (mask >> i) & 1 ? selc[i] : gl::sub(1, selc[i]);
-                    sel = i == 0 ? f : gl::mul(sel, f);
-                }
-            }
-            g0 = gl::mul(g0, sel);
-            g1 = gl::mul(g1, sel);
-        }
-        acc0 = gl::add(acc0, g0);
-        acc1 = gl::add(acc1, g1);
+        acc0 = gl::add(acc0, sink.g0);
+        acc1 = gl::add(acc1, sink.g1);
     }
     if (in) {
         dst0[L] = gl::canon(gl::add(acc0, dst0[L]));
@@ -179,15 +309,14 @@ __global__ __launch_bounds__(GT_THREADS) void gate_terms_kernel(const uint64_t* 
 // ------------------------------------------------------------------ satisfiability check
 // The same walk over trace columns (no LDE, no challenges, no accumulator): term k of row r fails
 // iff selector_g(r) * term_k(r) != 0, k being the running term index the alphas use (the segment's
-// alpha base carries it on).  One row of the window per lane; a lane past the window walks the
-// window's first row, so its loads stay in bounds, and counts nothing.  A lane keeps its number of
-// failures and the first failing k (k only grows, so the first is the smallest); a wave reduces
-// both with shuffles and, only if it saw a failure, issues one 64-bit add and one 64-bit min on the
-// status record: [0] += count, [1] = min(row << 32 | k).
+// alpha base carries it on).  One row of the window per lane.  A lane keeps its number of failures
+// and the first failing k (CheckSink); a wave reduces both with shuffles and, only if it saw a
+// failure, issues one 64-bit add and one 64-bit min on the status record: [0] += count,
+// [1] = min(row << 32 | k).
 //
-// VALUE = true is the second, one-wave launch of the call: every lane walks the row of the record's
-// key and lane 0 writes the canonical value of term k to [2] -- only when k lies in this segment
-// and the row in this window, so the value follows the key across the calls of a set.
+// gate_value_kernel is the second, one-wave launch of the call: every lane walks the row of the
+// record's key and lane 0 writes the canonical value of term k to [2] -- only when k lies in this
+// segment and the row in this window, so the value follows the key across the calls of a set.
 constexpr uint64_t GC_NONE = ~0ULL;
 constexpr uint32_t GC_WAVE = 64;
 
@@ -213,102 +342,47 @@ __device__ __forceinline__ void check_combine(uint64_t count, uint32_t first, si
     }
 }
 
-template <bool VALUE>
+template <class Program>
 __global__ __launch_bounds__(GT_THREADS) void gate_check_kernel(const uint64_t* __restrict__ seg, Cols cols,
                                                                 uint64_t row_begin, uint64_t n_rows,
                                                                 unsigned long long* __restrict__ status) {
-    __shared__ uint64_t lds[GT_SLOTS * GT_THREADS];
-    uint64_t* slots = lds + threadIdx.x;
-    uint32_t k = (uint32_t)uword(seg + 4);
     bool in;
-    size_t L;
-    uint32_t target = 0;
-    if constexpr (VALUE) {
-        const uint64_t key = uword(reinterpret_cast<const uint64_t*>(status) + 1);
-        const uint64_t row = key >> 32;
-        target = (uint32_t)key;
-        if (key == GC_NONE || target < k || target - k >= uword(seg + 5)) return;
-        if (row < row_begin || row - row_begin >= n_rows) return;
-        in = true;
-        L = (size_t)row;
-    } else {
-        const size_t l = blockIdx.x * (size_t)GT_THREADS + threadIdx.x;
-        in = l < n_rows;
-        L = (size_t)row_begin + (in ? l : 0);  // a lane past the window reads its first row and counts nothing
-    }
-
-    const uint32_t n_gates = (uint32_t)uword(seg + 0), n_instr = (uint32_t)uword(seg + 1);
-    const uint32_t n_writes = (uint32_t)uword(seg + 2), sel_cols = (uint32_t)uword(seg + 6);
-    const uint64_t* __restrict__ desc = seg + GT_HDR;
-    const uint64_t* __restrict__ instr = desc + (size_t)n_gates * GT_DESC;
-    const uint64_t* __restrict__ writes = instr + n_instr;
-    const uint64_t* __restrict__ imm = writes + n_writes;
-
-    uint64_t selc[GT_SEL];
-    if constexpr (!VALUE) {
-#pragma unroll
-        for (uint32_t i = 0; i < GT_SEL; i++) selc[i] = i < sel_cols ? cols.p[2][(size_t)i * cols.stride[2] + L] : 0;
-    }
-
-    uint64_t count = 0;
-    uint32_t first = 0;
+    const size_t L = lane_point(row_begin, n_rows, in);
+    Program prog(seg, cols, L, lane_slots<Program>());
+    prog.read_selector_columns();
+    CheckSink sink{1, 0, (uint32_t)uword(seg + 4), 0, false, in};
+    const uint32_t n_gates = gates_of<Program>(seg);
     for (uint32_t g = 0; g < n_gates; g++) {
-        const uint64_t* __restrict__ d = desc + (size_t)g * GT_DESC;
-        const uint64_t d0 = uword(d), d1 = uword(d + 1), d2 = uword(d + 2), mask = uword(d + 3);
-        const uint64_t dv = uword(d + 4), dw = uword(d + 5), dc = uword(d + 6);
-        const uint32_t i0 = (uint32_t)d0, i1 = (uint32_t)(d0 >> 32), w0 = (uint32_t)d1, w1 = (uint32_t)(d1 >> 32);
-        const uint32_t reps = (uint32_t)d2, depth = (uint32_t)(d2 >> 32);
-        uint32_t off[3] = {(uint32_t)dv, (uint32_t)dw, (uint32_t)dc};
-        uint64_t sel = 1;
-        if constexpr (!VALUE) {
-#pragma unroll
-            for (uint32_t i = 0; i < GT_SEL; i++) {
-                if (i < depth) {
-                    const uint64_t f = (mask >> i) & 1 ? selc[i] : gl::sub(1, selc[i]);
-                    sel = i == 0 ? f : gl::mul(sel, f);
-                }
-            }
-        }
-        for (uint32_t rep = 0; rep < reps; rep++) {
-            for (uint32_t pc = i0; pc < i1; pc++) {
-                const uint64_t w = uword(instr + pc);
-                const uint32_t op = (uint32_t)w & 0xff, slot = (uint32_t)(w >> 8) & 0xff;
-                const uint64_t a = fetch((uint32_t)(w >> 16) & 0xffffff, cols, off, L, slots, imm);
-                uint64_t r;
-                if (op == OP_DOUBLE) {
-                    r = gl::add(a, a);
-                } else if (op == OP_NEGATE) {
-                    r = gl::sub(0, a);
-                } else if (op == OP_SQUARE) {
-                    r = gl::mul(a, a);
-                } else {
-                    const uint64_t b = fetch((uint32_t)(w >> 40) & 0xffffff, cols, off, L, slots, imm);
-                    r = op == OP_MUL ? gl::mul(a, b) : op == OP_ADD ? gl::add(a, b) : gl::sub(a, b);
-                }
-                slots[slot * GT_THREADS] = r;
-            }
-            for (uint32_t t = w0; t < w1; t++, k++) {
-                const uint64_t v = fetch((uint32_t)uword(writes + t) & 0xffffff, cols, off, L, slots, imm);
-                if constexpr (VALUE) {
-                    if (k == target) {  // wave-uniform: every lane walks the same row
-                        if (threadIdx.x == 0) status[2] = gl::canon(v);
-                        return;
-                    }
-                } else {
-                    const bool fail = in && gl::canon(depth ? gl::mul(v, sel) : v) != 0;
-                    first = fail && count == 0 ? k : first;
-                    count += fail;
-                }
-            }
-            off[0] += (uint32_t)(dv >> 32);
-            off[1] += (uint32_t)(dw >> 32);
-            off[2] += (uint32_t)(dc >> 32);
-        }
+        const uint64_t* __restrict__ d = seg + GT_HDR + (size_t)g * GT_DESC;
+        const Placement pl(d);
+        prog.gate(d);
+        sink.selected = pl.depth != 0;  // the gate's selector is formed before its repetitions
+        sink.sel = selector(pl, prog);
+        repetitions(prog, pl, sink);
     }
-    if constexpr (!VALUE) check_combine(count, first, L, status);
+    check_combine(sink.count, sink.first, L, status);
 }
 
-#include "gates_poseidon2.hpp"
+template <class Program>
+__global__ __launch_bounds__(GT_THREADS) void gate_value_kernel(const uint64_t* __restrict__ seg, Cols cols,
+                                                                uint64_t row_begin, uint64_t n_rows,
+                                                                unsigned long long* __restrict__ status) {
+    const uint32_t k = (uint32_t)uword(seg + 4);
+    const uint64_t key = uword(reinterpret_cast<const uint64_t*>(status) + 1);
+    const uint64_t row = key >> 32;
+    const uint32_t target = (uint32_t)key;
+    if (key == GC_NONE || target < k || target - k >= uword(seg + 5)) return;
+    if (row < row_begin || row - row_begin >= n_rows) return;
+    Program prog(seg, cols, (size_t)row, lane_slots<Program>());  // no selector is formed: its columns stay unread
+    ValueSink sink{status, k, target};
+    const uint32_t n_gates = gates_of<Program>(seg);
+    for (uint32_t g = 0; g < n_gates && !sink.done(); g++) {  // the walk ends with the repetition of the target
+        const uint64_t* __restrict__ d = seg + GT_HDR + (size_t)g * GT_DESC;
+        const Placement pl(d);
+        prog.gate(d);
+        repetitions(prog, pl, sink);
+    }
+}
 
 // ------------------------------------------------------------------ host side: the image's checks
 struct Need {
@@ -344,6 +418,29 @@ bool operand_ok(uint32_t operand, uint64_t n_imm, uint32_t written, const uint64
     return true;
 }
 
+// A descriptor's placement, the same words for both kinds of gate, checked in two steps because a
+// native gate's own checks fire between them.  First [2] and [3]: the repetitions and the selector
+// path with its mask.
+int check_path(const uint64_t* d, uint64_t& reps, uint64_t& depth) {
+    reps = d[2] & 0xffffffff, depth = d[2] >> 32;
+    if (reps == 0 || reps > (1u << 20)) return bad("num_repetitions outside 1..2^20");
+    if (depth > GT_SEL || (d[3] >> depth)) return bad("malformed selector path");
+    return BJ_OK;
+}
+
+// Then [4] .. [6]: the three base | per << 32 column offsets.  width: the columns one repetition must
+// hold, per kind (a native gate's cells; nothing for a program, whose operands are checked one by one).
+// last: the offset at the largest repetition, at most 2^20 + 2^10 (2^20 - 1), well inside 2^31.
+int check_offsets(const uint64_t* d, uint64_t reps, const uint64_t (&width)[3], uint64_t (&last)[3]) {
+    for (int k = 0; k < 3; k++) {
+        const uint64_t b = d[4 + k] & 0xffffffff, per = d[4 + k] >> 32;
+        if (b > (1u << 20) || per > (1u << 10)) return bad("a column offset is out of range");
+        if (per < width[k]) return bad("a repetition of the native gate is narrower than its cells");
+        last[k] = b + per * (reps - 1);
+    }
+    return BJ_OK;
+}
+
 // A native segment (kind != 0): one gate, no program, the kind's own term count and cell split.
 int check_native(const uint64_t* seg, Need& need) {
     const uint64_t G = seg[0], I = seg[1], W = seg[2], M = seg[3], terms = seg[5], sel = seg[6], kind = seg[7];
@@ -351,23 +448,58 @@ int check_native(const uint64_t* seg, Need& need) {
     if (G != 1) return bad("a native segment holds exactly one gate");
     if (I || W || M) return bad("a native segment carries no instructions, writes or immediates");
     const uint64_t* d = seg + GT_HDR;
-    const uint64_t reps = d[2] & 0xffffffff, depth = d[2] >> 32, nw = d[7];
+    const uint64_t nw = d[7];
+    uint64_t reps, depth, last[3];
     if (d[0] != 0 || d[1] != (uint64_t)p2g::TERMS << 32) return bad("a native gate's instruction or write range is malformed");
-    if (reps == 0 || reps > (1u << 20)) return bad("num_repetitions outside 1..2^20");
-    if (depth > GT_SEL || (d[3] >> depth)) return bad("malformed selector path");
+    if (const int rc = check_path(d, reps, depth)) return rc;
     if (terms != p2g::TERMS * reps) return bad("a native segment's term count is not 118 per repetition");
     if (sel != depth) return bad("a segment's selector columns are not its deepest path");
     if (nw > p2g::MAX_WITNESS_CELLS) return bad("num_witness_columns_used exceeds the gate's 106 S-box output cells");
     const uint64_t width[3] = {p2g::CELLS - nw, nw, 0};
-    for (int k = 0; k < 3; k++) {
-        const uint64_t b = d[4 + k] & 0xffffffff, per = d[4 + k] >> 32;
-        if (b > (1u << 20) || per > (1u << 10)) return bad("a column offset is out of range");
-        if (per < width[k]) return bad("a repetition of the native gate is narrower than its cells");
-        const uint64_t reach = b + per * (reps - 1) + width[k];  // columns needed at the largest repetition
-        if (reach > ((uint64_t)1 << 31)) return bad("a column offset is out of range");
-        if (width[k] && reach > need.cols[k]) need.cols[k] = reach;
+    if (const int rc = check_offsets(d, reps, width, last)) return rc;
+    for (int k = 0; k < 2; k++)  // columns needed at the largest repetition
+        if (width[k] && last[k] + width[k] > need.cols[k]) need.cols[k] = last[k] + width[k];
+    return BJ_OK;
+}
+
+// An interpreted segment: every gate's ranges and placement, every instruction and write.
+int check_interpreted(const uint64_t* seg, Need& need) {
+    const uint64_t G = seg[0], I = seg[1], W = seg[2], M = seg[3], terms = seg[5], sel = seg[6];
+    const uint64_t* desc = seg + GT_HDR;
+    const uint64_t* instr = desc + G * GT_DESC;
+    const uint64_t* writes = instr + I;
+    uint64_t count = 0, deepest = 0;
+    for (uint64_t g = 0; g < G; g++) {
+        const uint64_t* d = desc + g * GT_DESC;
+        const uint64_t i0 = d[0] & 0xffffffff, i1 = d[0] >> 32, w0 = d[1] & 0xffffffff, w1 = d[1] >> 32;
+        uint64_t reps, depth, last[3];
+        if (i0 > i1 || i1 > I || w0 >= w1 || w1 > W) return bad("a gate's instruction or write range is malformed or has no terms");
+        if (const int rc = check_path(d, reps, depth)) return rc;
+        if (d[7] != 0) return bad("malformed selector path");
+        if (depth > deepest) deepest = depth;
+        if (const int rc = check_offsets(d, reps, {0, 0, 0}, last)) return rc;
+        uint32_t written = 0;
+        for (uint64_t pc = i0; pc < i1; pc++) {
+            const uint64_t w = instr[pc];
+            const uint32_t op = (uint32_t)(w & 0xff), slot = (uint32_t)((w >> 8) & 0xff);
+            if (op == 6) return bad("Relation::Inverse is not evaluated (no evaluator in cs/gates records it)");
+            if (op > 6) return bad("unknown opcode");
+            if (slot >= GT_SLOTS) return bad("more temporaries live at once than BJ_GATE_MAX_SLOTS");
+            const bool unary = op == OP_DOUBLE || op == OP_NEGATE || op == OP_SQUARE;
+            if (!operand_ok((uint32_t)((w >> 16) & 0xffffff), M, written, last, need) ||
+                (!unary && !operand_ok((uint32_t)((w >> 40) & 0xffffff), M, written, last, need)))
+                return bad("an operand is outside its space, or a temporary is read before it is written");
+            if (unary && (w >> 40)) return bad("a unary relation carries a second operand");
+            written |= 1u << slot;
+        }
+        for (uint64_t t = w0; t < w1; t++) {
+            if (writes[t] >> 24 || !operand_ok((uint32_t)writes[t], M, written, last, need))
+                return bad("a written operand is outside its space, or a temporary that was never written");
+        }
+        count += reps * (w1 - w0);
     }
-    if (sel > need.cols[K_CONST]) need.cols[K_CONST] = sel;
+    if (count != terms) return bad("a segment's term count is not the sum over its gates");
+    if (sel != deepest) return bad("a segment's selector columns are not its deepest path");
     return BJ_OK;
 }
 
@@ -391,52 +523,7 @@ int check_image(const uint64_t* image, size_t words, Need& need, uint64_t* seg_o
         if (sel > GT_SEL) return bad("selector depth exceeds BJ_GATE_MAX_SELECTOR_DEPTH");
         if (base != need.alphas) return bad("a segment's alpha base is not the sum of the terms before it");
         if (seg_kind) seg_kind[s] = seg[7];
-        if (seg[7] != 0) {
-            if (const int rc = check_native(seg, need)) return rc;
-            need.alphas += terms;
-            if (seg_offset) seg_offset[s] = at;
-            continue;
-        }
-        const uint64_t* desc = seg + GT_HDR;
-        const uint64_t* instr = desc + G * GT_DESC;
-        const uint64_t* writes = instr + I;
-        uint64_t count = 0, deepest = 0;
-        for (uint64_t g = 0; g < G; g++) {
-            const uint64_t* d = desc + g * GT_DESC;
-            const uint64_t i0 = d[0] & 0xffffffff, i1 = d[0] >> 32, w0 = d[1] & 0xffffffff, w1 = d[1] >> 32;
-            const uint64_t reps = d[2] & 0xffffffff, depth = d[2] >> 32;
-            if (i0 > i1 || i1 > I || w0 >= w1 || w1 > W) return bad("a gate's instruction or write range is malformed or has no terms");
-            if (reps == 0 || reps > (1u << 20)) return bad("num_repetitions outside 1..2^20");
-            if (depth > GT_SEL || (depth < 64 && (d[3] >> depth)) || d[7] != 0) return bad("malformed selector path");
-            if (depth > deepest) deepest = depth;
-            uint64_t last[3];
-            for (int k = 0; k < 3; k++) {
-                const uint64_t b = d[4 + k] & 0xffffffff, per = d[4 + k] >> 32;
-                if (b > (1u << 20) || per > (1u << 10)) return bad("a column offset is out of range");
-                last[k] = b + per * (reps - 1);
-            }
-            uint32_t written = 0;
-            for (uint64_t pc = i0; pc < i1; pc++) {
-                const uint64_t w = instr[pc];
-                const uint32_t op = (uint32_t)(w & 0xff), slot = (uint32_t)((w >> 8) & 0xff);
-                if (op == 6) return bad("Relation::Inverse is not evaluated (no evaluator in cs/gates records it)");
-                if (op > 6) return bad("unknown opcode");
-                if (slot >= GT_SLOTS) return bad("more temporaries live at once than BJ_GATE_MAX_SLOTS");
-                const bool unary = op == OP_DOUBLE || op == OP_NEGATE || op == OP_SQUARE;
-                if (!operand_ok((uint32_t)((w >> 16) & 0xffffff), M, written, last, need) ||
-                    (!unary && !operand_ok((uint32_t)((w >> 40) & 0xffffff), M, written, last, need)))
-                    return bad("an operand is outside its space, or a temporary is read before it is written");
-                if (unary && (w >> 40)) return bad("a unary relation carries a second operand");
-                written |= 1u << slot;
-            }
-            for (uint64_t t = w0; t < w1; t++) {
-                if (writes[t] >> 24 || !operand_ok((uint32_t)writes[t], M, written, last, need))
-                    return bad("a written operand is outside its space, or a temporary that was never written");
-            }
-            count += reps * (w1 - w0);
-        }
-        if (count != terms) return bad("a segment's term count is not the sum over its gates");
-        if (sel != deepest) return bad("a segment's selector columns are not its deepest path");
+        if (const int rc = seg[7] ? check_native(seg, need) : check_interpreted(seg, need)) return rc;
         if (sel > need.cols[K_CONST]) need.cols[K_CONST] = sel;
         need.alphas += terms;
         if (seg_offset) seg_offset[s] = at;
@@ -542,9 +629,10 @@ int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* 
         return rc;
     if (s->need.alphas > n_alphas) return bj::set_error(BJ_EINVAL, "gate program: fewer challenges than terms");
     const size_t blocks = (total + bj::GT_THREADS - 1) / bj::GT_THREADS;
-    hipLaunchKernelGGL(s->seg_kind[segment] ? bj::p2g::gate_terms_kernel : bj::gate_terms_kernel, dim3((unsigned)blocks),
-                       dim3(bj::GT_THREADS), 0, bj::S(stream), s->image_d + s->seg_offset[segment], cols, alphas, total,
-                       dst0, dst1);
+    hipLaunchKernelGGL(
+        s->seg_kind[segment] ? bj::gate_terms_kernel<bj::p2g::Program> : bj::gate_terms_kernel<bj::Interpreter>,
+        dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, bj::S(stream), s->image_d + s->seg_offset[segment], cols,
+        alphas, total, dst0, dst1);
     return bj::ok_or(hipGetLastError(), "quotient gate terms");
 }
 
@@ -574,10 +662,10 @@ int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* v
     if (begin) hipLaunchKernelGGL(bj::gate_check_begin_kernel, dim3(1), dim3(bj::GC_WAVE), 0, st, status);
     const size_t blocks = (size_t)((n_rows + bj::GT_THREADS - 1) / bj::GT_THREADS);
     const bool native = s->seg_kind[segment] != 0;
-    hipLaunchKernelGGL(native ? bj::p2g::gate_check_kernel<false> : bj::gate_check_kernel<false>, dim3((unsigned)blocks),
-                       dim3(bj::GT_THREADS), 0, st, seg, cols, row_begin, n_rows, status);
-    hipLaunchKernelGGL(native ? bj::p2g::gate_check_kernel<true> : bj::gate_check_kernel<true>, dim3(1),
-                       dim3(bj::GC_WAVE), 0, st, seg, cols, row_begin, n_rows, status);
+    hipLaunchKernelGGL(native ? bj::gate_check_kernel<bj::p2g::Program> : bj::gate_check_kernel<bj::Interpreter>,
+                       dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, st, seg, cols, row_begin, n_rows, status);
+    hipLaunchKernelGGL(native ? bj::gate_value_kernel<bj::p2g::Program> : bj::gate_value_kernel<bj::Interpreter>,
+                       dim3(1), dim3(bj::GC_WAVE), 0, st, seg, cols, row_begin, n_rows, status);
     return bj::ok_or(hipGetLastError(), "gate set satisfiability check");
 }
 

@@ -19,8 +19,9 @@
 // the element shifted by SH; every constant is the reference's (poseidon2/params.rs).  Values are
 // u64 representatives, any on input; what a sink keeps is canonicalised where it leaves the kernel.
 //
-// Included by gates.hip inside namespace bj's unnamed namespace, after Cols, uword, check_combine and
-// the GT_ / GC_ constants it uses.
+// This file holds the gate's own: constants, matrices, S-boxes, the walk and the program kind that hands
+// it to the frames.  Placement, selector, sinks and the three kernels are gates.hip's, which includes this
+// inside namespace bj's unnamed namespace, after Cols and Placement; it needs gl.hpp and ext2.hpp.
 #pragma once
 
 namespace p2g {
@@ -167,119 +168,28 @@ __device__ __forceinline__ void walk(const Instance& at, size_t L, Sink& sink) {
     for (uint32_t i = 0; i < SW; i++) sink.emit(gl::sub(at.variable(SW + i, L), x[i]));
 }
 
-// What a kernel reads of the segment's one descriptor, in scalar registers.
-struct Placement {
-    uint32_t reps, depth, base[2], per[2], nw;
-    uint64_t mask;
+// The program kind the frames of gates.hip are instantiated with: one descriptor, nothing per gate,
+// the selector columns loaded as they are met (a rolled loop), word [7] of the placement the split.
+struct Program {
+    static constexpr uint32_t SELECTOR_UNROLL = 1;
+    static constexpr uint32_t GATES = 1;
+    static constexpr uint32_t SLOTS = 0;
+    const Cols& cols;
+    const size_t L;
 
-    __device__ __forceinline__ explicit Placement(const uint64_t* __restrict__ seg) {
-        const uint64_t* __restrict__ d = seg + GT_HDR;
-        const uint64_t d2 = uword(d + 2), dv = uword(d + 4), dw = uword(d + 5);
-        reps = (uint32_t)d2, depth = (uint32_t)(d2 >> 32), mask = uword(d + 3);
-        base[0] = (uint32_t)dv, per[0] = (uint32_t)(dv >> 32);
-        base[1] = (uint32_t)dw, per[1] = (uint32_t)(dw >> 32);
-        nw = (uint32_t)uword(d + 7);
+    __device__ __forceinline__ Program(const uint64_t* __restrict__, const Cols& cols, size_t L, uint64_t*)
+        : cols(cols), L(L) {}
+    __device__ __forceinline__ void gate(const uint64_t* __restrict__) {}
+    __device__ __forceinline__ void read_selector_columns() {}
+    __device__ __forceinline__ uint64_t selector_column(uint32_t i) const {
+        return cols.p[2][(size_t)i * cols.stride[2] + L];
     }
-    __device__ __forceinline__ Instance instance(const Cols& cols, uint32_t rep) const {
-        return Instance{cols.p[0] + (size_t)(base[0] + rep * per[0]) * cols.stride[0],
-                        cols.p[1] + (size_t)(base[1] + rep * per[1]) * cols.stride[1], cols.stride[0], cols.stride[1],
-                        nw};
-    }
-    // the path product over constant columns 0 .. depth - 1 (depth > 0), as the interpreter forms it
-    __device__ __forceinline__ uint64_t selector(const Cols& cols, size_t L) const {
-        uint64_t sel = 1;
-#pragma unroll 1
-        for (uint32_t i = 0; i < depth; i++) {
-            const uint64_t c = cols.p[2][(size_t)i * cols.stride[2] + L];
-            const uint64_t f = (mask >> i) & 1 ? c : gl::sub(1, c);
-            sel = i == 0 ? f : gl::mul(sel, f);
-        }
-        return sel;
+    template <class Sink>
+    __device__ __forceinline__ void walk(const Placement& pl, const uint32_t (&off)[3], Sink& sink) const {
+        p2g::walk(Instance{cols.p[0] + (size_t)off[0] * cols.stride[0], cols.p[1] + (size_t)off[1] * cols.stride[1],
+                           cols.stride[0], cols.stride[1], pl.word7},
+                  L, sink);
     }
 };
-
-// acc += alpha[k] term, two base products, k running on from the segment's alpha base
-struct AccumulatorSink {
-    const uint64_t* __restrict__ alpha;
-    uint64_t g0, g1;
-    __device__ __forceinline__ void emit(uint64_t v) {
-        g0 = gl::add(g0, gl::mul(v, uword(alpha)));
-        g1 = gl::add(g1, gl::mul(v, uword(alpha + 1)));
-        alpha += 2;
-    }
-};
-
-// the lane's number of failing terms and the first of them, by the rule of gate_check_kernel
-struct CheckSink {
-    uint64_t sel, count;
-    uint32_t k, first;
-    bool selected, in;
-    __device__ __forceinline__ void emit(uint64_t v) {
-        const bool fail = in && gl::canon(selected ? gl::mul(v, sel) : v) != 0;
-        first = fail && count == 0 ? k : first;
-        count += fail;
-        k++;
-    }
-};
-
-// the canonical value of term `target` to the record (every lane walks the same row)
-struct ValueSink {
-    unsigned long long* __restrict__ status;
-    uint32_t k, target;
-    __device__ __forceinline__ void emit(uint64_t v) {
-        if (k == target && threadIdx.x == 0) status[2] = gl::canon(v);
-        k++;
-    }
-};
-
-// bj_quotient_gate_terms_d on a native segment: gate_terms_kernel's contract, one point per lane.
-__global__ __launch_bounds__(GT_THREADS) void gate_terms_kernel(const uint64_t* __restrict__ seg, Cols cols,
-                                                                const uint64_t* __restrict__ alphas, size_t total,
-                                                                uint64_t* __restrict__ dst0,
-                                                                uint64_t* __restrict__ dst1) {
-    const size_t l = blockIdx.x * (size_t)GT_THREADS + threadIdx.x;
-    const bool in = l < total;
-    const size_t L = in ? l : 0;  // a lane past the end reads point 0 and writes nothing
-    const Placement pl(seg);
-    AccumulatorSink sink{alphas + 2 * uword(seg + 4), 0, 0};
-#pragma unroll 1
-    for (uint32_t rep = 0; rep < pl.reps; rep++) walk(pl.instance(cols, rep), L, sink);
-    if (pl.depth) {  // the selector multiplies the gate's sum once
-        const uint64_t sel = pl.selector(cols, L);
-        sink.g0 = gl::mul(sink.g0, sel);
-        sink.g1 = gl::mul(sink.g1, sel);
-    }
-    if (in) {
-        dst0[L] = gl::canon(gl::add(sink.g0, dst0[L]));
-        dst1[L] = gl::canon(gl::add(sink.g1, dst1[L]));
-    }
-}
-
-// bj_gate_set_satisfied_d on a native segment: gate_check_kernel's contract and its two launches.
-template <bool VALUE>
-__global__ __launch_bounds__(GT_THREADS) void gate_check_kernel(const uint64_t* __restrict__ seg, Cols cols,
-                                                                uint64_t row_begin, uint64_t n_rows,
-                                                                unsigned long long* __restrict__ status) {
-    const uint32_t k = (uint32_t)uword(seg + 4);
-    const Placement pl(seg);
-    if constexpr (VALUE) {
-        const uint64_t key = uword(reinterpret_cast<const uint64_t*>(status) + 1);
-        const uint64_t row = key >> 32;
-        const uint32_t target = (uint32_t)key;
-        if (key == GC_NONE || target < k || target - k >= uword(seg + 5)) return;
-        if (row < row_begin || row - row_begin >= n_rows) return;
-        ValueSink sink{status, k, target};
-#pragma unroll 1
-        for (uint32_t rep = 0; rep < pl.reps; rep++) walk(pl.instance(cols, rep), (size_t)row, sink);
-    } else {
-        const size_t l = blockIdx.x * (size_t)GT_THREADS + threadIdx.x;
-        const bool in = l < n_rows;
-        const size_t L = (size_t)row_begin + (in ? l : 0);  // a lane past the window reads its first row
-        CheckSink sink{pl.depth ? pl.selector(cols, L) : 1, 0, k, 0, pl.depth != 0, in};
-#pragma unroll 1
-        for (uint32_t rep = 0; rep < pl.reps; rep++) walk(pl.instance(cols, rep), L, sink);
-        check_combine(sink.count, sink.first, L, status);
-    }
-}
 
 }  // namespace p2g

@@ -8,6 +8,9 @@ tests/test_host_errors.py holds the changed code to the earlier behaviour.
 
 The host cases need no GPU.  The device cases (a local group's events) are recorded only with --device,
 on a machine with one; without it their earlier entries in the file are kept.
+
+--cases names another module of cases in the same format, with --out its golden: the gate-set validator's are
+tests/gate_check_cases.py and tests/golden/gate_check_errors.json.
 """
 import argparse
 import ctypes
@@ -25,9 +28,11 @@ def main():
     ap.add_argument("--lib", required=True, help="libboojum_mi355x.so built at the earlier commit")
     ap.add_argument("--device", action="store_true", help="record the cases that need a GPU as well")
     ap.add_argument("--out", default=GOLDEN)
+    ap.add_argument("--cases", default="host_error_cases", help="the module under tests/ that holds the cases")
     args = ap.parse_args()
     from boojum_amd import _lib
-    import host_error_cases as cases
+    import importlib
+    cases = importlib.import_module(args.cases)
     L = ctypes.CDLL(os.path.abspath(args.lib))
     for name, (argtypes, restype) in _lib.SIGNATURES.items():
         fn = getattr(L, name)
