@@ -123,6 +123,7 @@ SIGNATURES = {
     "bj_vanishing_inverses_h": ([_u32, _u32, _u64p], _int),
     "bj_gate_set_check_h": ([_u64p, _sz, _u64p], _int),
     "bj_gate_native_info_h": ([_u32, _u64p], _int),
+    "bj_gate_library_find_h": ([ctypes.c_char_p, _u64p], _int),
     "bj_gate_set_upload_d": ([_u64p, _sz, ctypes.POINTER(_vp)], _int),
     "bj_gate_set_release": ([_vp], _int),
     "bj_quotient_gate_terms_d": ([_vp, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _sz, _u32, _vp, _u32, _u32, _u32,
@@ -147,7 +148,7 @@ SIGNATURES = {
 }
 
 # Added after 2.6 and detected by symbol: a library without one of these still loads.
-OPTIONAL = ("bj_gate_native_info_h",)
+OPTIONAL = ("bj_gate_native_info_h", "bj_gate_library_find_h")
 
 
 class CommInfo(ctypes.Structure):

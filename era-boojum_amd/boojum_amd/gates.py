@@ -17,6 +17,10 @@ gpu_synthesizer/mod.rs captures from an evaluator's `evaluate_once`:
 * native segments: an evaluator that declares a `native_kind` (`Poseidon2FlattenedGate`, whose
   capture passes every cap of a launch) is not captured; it gets a segment of its own that names the
   kind, and the library runs a written-out kernel on it (csrc/gates_poseidon2.hpp);
+* library segments (opt-in, `native_library=True`): a captured gate whose `program_digest` equals
+  the one the library stores under the evaluator's name (`library_gate_info`) goes into a segment of
+  kind 3 that names it by id, and the library runs the straight-line code generated from that
+  capture (tools/gen_gate_library.py -> csrc/gates_library.hpp);
 * `evaluate_gate_terms`: dst += the gate terms, one launch per segment;
 * `check_if_satisfied` -> `SatisfiabilityReport`: the reference's check_if_satisfied
   (cs/implementations/satisfiability_test.rs:15-353) over the trace columns, on the device
@@ -45,6 +49,7 @@ MAX_GATES = 64              # BJ_GATE_MAX_GATES
 MAX_SEGMENTS = 64           # BJ_GATE_MAX_SEGMENTS
 MAGIC = 0x3153455441474A42  # "BJGATES1"
 KIND_INTERPRETED, KIND_POSEIDON2 = 0, 1   # word [7] of a segment head
+KIND_LIBRARY = 3                          # a segment of library gates (csrc/gates_library.hpp); 2 stays refused
 
 _KINDS = ("VariablePoly", "WitnessPoly", "ConstantPoly", "TemporaryValue", "ConstantValue")
 _RELATIONS = ("Add", "Double", "Sub", "Negate", "Mul", "Square", "Inverse")
@@ -224,6 +229,38 @@ def capture(evaluator):
     return GateProgram(ctx.relations, dst.writes, evaluator.num_quotient_terms, evaluator)
 
 
+_FNV_OFFSET, _FNV_PRIME = 0xCBF29CE484222325, 0x100000001B3
+
+
+def program_digest(program):
+    """FNV-1a-64 of a captured program, the number the library stores per gate it has generated code for
+    (tools/gen_gate_library.py -> csrc/gates_library.hpp) and compile_gate_set compares before it lets a
+    placement name a library entry.  The bytes hashed, integers little-endian:
+
+      u32 number of relations, u32 number of writes,
+      per relation in order: u8 opcode (Relation's order: 0 Add .. 6 Inverse), u32 destination
+      TemporaryValue index, u8 number of operands, then per operand u8 kind (Index's order:
+      0 VariablePoly, 1 WitnessPoly, 2 ConstantPoly, 3 TemporaryValue, 4 ConstantValue) and u64 value
+      (the index, or the canonical constant),
+      u8 0xFF,
+      per write in push order: u8 kind, u64 value.
+
+    Names, placement and num_quotient_terms (the number of writes) are not part of it."""
+    def operand(o):
+        return bytes([_KINDS.index(o.kind)]) + int(o.value).to_bytes(8, "little")
+
+    data = [len(program.relations).to_bytes(4, "little"), len(program.writes).to_bytes(4, "little")]
+    for dst, rel in program.relations:
+        data.append(bytes([_RELATIONS.index(rel.kind)]) + int(dst).to_bytes(4, "little") + bytes([len(rel.operands)]))
+        data += [operand(o) for o in rel.operands]
+    data.append(b"\xff")
+    data += [operand(o) for o in program.writes]
+    h = _FNV_OFFSET
+    for byte in b"".join(data):
+        h = (h ^ byte) * _FNV_PRIME & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
 class NativeGateProgram:
     """What stands for the capture of an evaluator with a native kind: nothing is recorded, the
     library knows the gate."""
@@ -249,6 +286,17 @@ def native_gate_info(kind):
     fn = getattr(load(), "bj_gate_native_info_h", None)
     out = (ctypes.c_uint64 * 4)()
     if fn is None or fn(kind, out) != 0:
+        return None
+    return tuple(int(v) for v in out)
+
+
+def library_gate_info(name):
+    """bj_gate_library_find_h: (id, terms per repetition, variable, witness and constant columns one
+    repetition reads, digest of the capture the code was generated from) of the library gate `name`,
+    or None when the library is older than library segments or does not know the name."""
+    fn = getattr(load(), "bj_gate_library_find_h", None)
+    out = (ctypes.c_uint64 * 6)()
+    if fn is None or name is None or fn(str(name).encode(), out) != 0:
         return None
     return tuple(int(v) for v in out)
 
@@ -457,12 +505,38 @@ def _encode_native(seg, pl, kind):
     seg.depth = len(pl.selector_path)
 
 
-def compile_gate_set(placements, slot_cap=MAX_SLOTS):
+def _library_entry(pl):
+    """The library's entry for a placement's gate -- bj_gate_library_find_h's tuple -- or None: the
+    evaluator has a native kind of its own, the library does not know its name, or the capture is
+    not the one the library's code was generated from (a same-named evaluator that records other
+    relations stays interpreted)."""
+    prog = pl.program
+    if _native_kind(pl) or prog.evaluator is None or prog.relations is None:
+        return None
+    info = library_gate_info(prog.evaluator.name)
+    if info is None or info[1] != prog.num_quotient_terms or info[5] != program_digest(prog):
+        return None
+    return info
+
+
+def _encode_library(seg, pl, info):
+    """One gate of a library segment: [0] the library id, [1] the terms per repetition with no writes
+    behind them, [2] .. [6] the placement as for every gate, [7] 0."""
+    seg.desc += [info[0], info[1] << 32] + _placement_words(pl) + [0]
+    seg.kind = KIND_LIBRARY
+    seg.terms += pl.num_terms()
+    seg.depth = max(seg.depth, len(pl.selector_path))
+
+
+def compile_gate_set(placements, slot_cap=MAX_SLOTS, native_library=False):
     """Placements in evaluation order -> the upload image, a list of u64 words
     (include/boojum_mi355x.h, "quotient gate terms").  Gates fill a segment until a cap of one launch
     would be passed; the next segment's alpha base carries the challenge index on.  A placement
     whose evaluator declares a native kind closes the segment before it and takes one of its own,
-    uncaptured.  Host only."""
+    uncaptured.  With native_library, a placement whose capture is one the library has generated code
+    for (_library_entry) goes into a library segment instead of an interpreted one; consecutive ones
+    share a segment of up to MAX_GATES gates.  The order of the placements, and so the challenge
+    index, is the same whatever the kinds.  Host only."""
     placements = list(placements)
     if not placements:
         raise ValueError("a gate set holds at least one gate with quotient terms")
@@ -477,15 +551,23 @@ def compile_gate_set(placements, slot_cap=MAX_SLOTS):
     for pl in placements:
         if pl.program.num_quotient_terms == 0:
             raise ValueError("a gate without quotient terms never reaches the library (prover.rs:922-994)")
+        entry = _library_entry(pl) if native_library else None
         if _native_kind(pl):
             close()
             _encode_native(seg, pl, _native_kind(pl))
             close()
-        elif not _encode_gate(seg, pl, slot_cap):
-            empty = not seg.desc   # an empty segment did not take the gate: none will
-            close()
-            if empty or not _encode_gate(seg, pl, slot_cap):
-                raise ValueError("one gate exceeds the caps of a launch")
+        elif entry is not None:
+            if seg.kind != KIND_LIBRARY or len(seg.desc) // 8 == MAX_GATES:
+                close()
+            _encode_library(seg, pl, entry)
+        else:
+            if seg.kind == KIND_LIBRARY:
+                close()
+            if not _encode_gate(seg, pl, slot_cap):
+                empty = not seg.desc   # an empty segment did not take the gate: none will
+                close()
+                if empty or not _encode_gate(seg, pl, slot_cap):
+                    raise ValueError("one gate exceeds the caps of a launch")
     close()
     image = [MAGIC, len(segments)] + [0] * len(segments)
     for i, s in enumerate(segments):
@@ -543,12 +625,13 @@ class TermMap:
 
 class GateSet:
     """Slot allocation, validation and the single upload of a gate set; keeps the device buffer
-    alive until it is collected or `release()`d.  `GateSet.from_image` uploads a prepared image."""
+    alive until it is collected or `release()`d.  `GateSet.from_image` uploads a prepared image.
+    native_library: compile_gate_set's flag, library segments for the gates the library has code for."""
 
-    def __init__(self, placements, slot_cap=MAX_SLOTS):
+    def __init__(self, placements, slot_cap=MAX_SLOTS, native_library=False):
         self._handle = None
         self.placements = list(placements)
-        self._upload(compile_gate_set(self.placements, slot_cap))
+        self._upload(compile_gate_set(self.placements, slot_cap, native_library))
 
     @classmethod
     def from_image(cls, image):

@@ -31,7 +31,8 @@
 //   [0] GT_MAGIC  [1] number of segments S  [2 .. 2 + S) word offset of each segment
 //   segment: [0] gates G  [1] instructions I  [2] writes W  [3] immediates M  [4] alpha base
 //            [5] terms (sum over gates of repetitions * writes)  [6] selector columns read
-//            [7] kind: 0 interpreted, 1 native Poseidon2 flattened gate (gates_poseidon2.hpp)
+//            [7] kind: 0 interpreted, 1 native Poseidon2 flattened gate (gates_poseidon2.hpp),
+//            3 library gates (gates_library.hpp); 2 is no kind
 //            G descriptors of 8 words, I instructions, W writes, M immediates
 //   descriptor: [0] instr begin | end << 32   [1] write begin | end << 32
 //               [2] repetitions | path length << 32   [3] path bit mask (bit i set: take column i,
@@ -47,8 +48,13 @@
 //
 // A native segment holds one gate of a kind whose walk is written out (kind 1, p2g::Program, no LDS):
 // G = 1, I = W = M = 0, the descriptor's [0] is 0 and its [1] is 0 | terms per repetition << 32 with
-// no writes behind it, [2] .. [6] keep their meaning.  The two entry points pick the frame's
-// instantiation by the kind.
+// no writes behind it, [2] .. [6] keep their meaning.
+//
+// A library segment (kind 3, lib::Program, no LDS) holds 1 .. GT_GATES gates the library has generated
+// straight-line code for (tools/gen_gate_library.py -> gates_library.hpp, from the captures of
+// boojum_amd.gates.library()): I = W = M = 0, a descriptor's [0] is the library id, its [1] is
+// 0 | terms per repetition << 32, [2] .. [6] keep their meaning and [7] is 0.  The two entry points
+// pick the frame's instantiation by the kind.
 //
 // One call launches one segment.  A gate set over the caps is split into segments by the caller,
 // which is exact because the call adds to the accumulator and a segment carries its alpha base.
@@ -57,6 +63,7 @@
 // cs/implementations/satisfiability_test.rs:15-353): gate_check_kernel walks the same programs over
 // trace rows and reports the count and the first failing (row, term) in a status record.
 #include <hip/hip_runtime.h>
+#include <cstring>
 #include <new>
 #include "ext2.hpp"
 #include "gl.hpp"
@@ -169,6 +176,7 @@ struct ValueSink {
 // sink) for one repetition of that gate at L and the repetition's three column offsets, and the point's
 // selector columns (read_selector_columns() once where a frame forms selectors, then selector_column(i)).
 #include "gates_poseidon2.hpp"
+#include "gates_library.hpp"
 
 // Kind 0: the relation programs of the image, temporaries in this lane's column of the LDS slots.
 struct Interpreter {
@@ -462,6 +470,43 @@ int check_native(const uint64_t* seg, Need& need) {
     return BJ_OK;
 }
 
+// A library segment (kind 3): every gate's placement first, as for the other kinds, then what is the
+// kind's own -- no program area, a known id with its term count, word [7] clear, the sums of the head.
+// need: what the largest repetition reaches, as the operands of the interpreted program would claim it.
+namespace refusal {  // the kind's own refusals by name; tests/test_gate_library_cpu.py holds an image for each
+constexpr const char* PROGRAM_AREA = "a library segment carries no instructions, writes or immediates";
+constexpr const char* UNKNOWN_ID = "unknown library gate id";
+constexpr const char* GATE_TERMS = "a library gate's term count is not its entry's";
+constexpr const char* WORD7 = "word [7] of a library gate is not 0";
+}  // namespace refusal
+
+int check_library(const uint64_t* seg, Need& need) {
+    const uint64_t G = seg[0], I = seg[1], W = seg[2], M = seg[3], terms = seg[5], sel = seg[6];
+    const uint64_t* desc = seg + GT_HDR;
+    uint64_t count = 0, deepest = 0;
+    uint64_t reps[GT_GATES], last[GT_GATES][3];  // G <= GT_GATES: check_image
+    for (uint64_t g = 0; g < G; g++) {
+        uint64_t depth;
+        if (const int rc = check_path(desc + g * GT_DESC, reps[g], depth)) return rc;
+        if (const int rc = check_offsets(desc + g * GT_DESC, reps[g], {0, 0, 0}, last[g])) return rc;
+        if (depth > deepest) deepest = depth;
+    }
+    if (I || W || M) return bad(refusal::PROGRAM_AREA);
+    for (uint64_t g = 0; g < G; g++) {
+        const uint64_t* d = desc + g * GT_DESC;
+        if (d[0] == 0 || d[0] > lib::ENTRIES) return bad(refusal::UNKNOWN_ID);
+        const lib::Entry& e = lib::TABLE[d[0] - 1];
+        if (d[1] != (uint64_t)e.terms << 32) return bad(refusal::GATE_TERMS);
+        if (d[7] != 0) return bad(refusal::WORD7);
+        for (int k = 0; k < 3; k++)  // columns needed at the largest repetition
+            if (e.columns[k] && last[g][k] + e.columns[k] > need.cols[k]) need.cols[k] = last[g][k] + e.columns[k];
+        count += reps[g] * e.terms;
+    }
+    if (count != terms) return bad("a segment's term count is not the sum over its gates");
+    if (sel != deepest) return bad("a segment's selector columns are not its deepest path");
+    return BJ_OK;
+}
+
 // An interpreted segment: every gate's ranges and placement, every instruction and write.
 int check_interpreted(const uint64_t* seg, Need& need) {
     const uint64_t G = seg[0], I = seg[1], W = seg[2], M = seg[3], terms = seg[5], sel = seg[6];
@@ -523,7 +568,10 @@ int check_image(const uint64_t* image, size_t words, Need& need, uint64_t* seg_o
         if (sel > GT_SEL) return bad("selector depth exceeds BJ_GATE_MAX_SELECTOR_DEPTH");
         if (base != need.alphas) return bad("a segment's alpha base is not the sum of the terms before it");
         if (seg_kind) seg_kind[s] = seg[7];
-        if (const int rc = seg[7] ? check_native(seg, need) : check_interpreted(seg, need)) return rc;
+        const int rc = seg[7] == lib::KIND ? check_library(seg, need)
+                       : seg[7]           ? check_native(seg, need)
+                                          : check_interpreted(seg, need);
+        if (rc) return rc;
         if (sel > need.cols[K_CONST]) need.cols[K_CONST] = sel;
         need.alphas += terms;
         if (seg_offset) seg_offset[s] = at;
@@ -575,6 +623,18 @@ int bj_gate_native_info_h(uint32_t kind, uint64_t* out) {
     if (!out) return bj::set_error(BJ_EINVAL, "bj_gate_native_info_h: null out");
     out[0] = bj::p2g::CELLS, out[1] = bj::p2g::TERMS, out[2] = bj::p2g::DEGREE, out[3] = bj::p2g::MAX_WITNESS_CELLS;
     return BJ_OK;
+}
+
+int bj_gate_library_find_h(const char* name, uint64_t* out) {
+    if (!name) return bj::set_error(BJ_EINVAL, "bj_gate_library_find_h: null name");
+    if (!out) return bj::set_error(BJ_EINVAL, "bj_gate_library_find_h: null out");
+    for (const bj::lib::Entry& e : bj::lib::TABLE) {
+        if (strcmp(name, e.name) != 0) continue;
+        out[0] = e.id, out[1] = e.terms, out[2] = e.columns[0], out[3] = e.columns[1], out[4] = e.columns[2];
+        out[5] = e.digest;
+        return BJ_OK;
+    }
+    return bj::set_error(BJ_EINVAL, "bj_gate_library_find_h: no library gate of that name");
 }
 
 int bj_gate_set_upload_d(const uint64_t* image, size_t words, void** set) {
@@ -629,10 +689,12 @@ int bj_quotient_gate_terms_d(const void* set, uint32_t segment, const uint64_t* 
         return rc;
     if (s->need.alphas > n_alphas) return bj::set_error(BJ_EINVAL, "gate program: fewer challenges than terms");
     const size_t blocks = (total + bj::GT_THREADS - 1) / bj::GT_THREADS;
-    hipLaunchKernelGGL(
-        s->seg_kind[segment] ? bj::gate_terms_kernel<bj::p2g::Program> : bj::gate_terms_kernel<bj::Interpreter>,
-        dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, bj::S(stream), s->image_d + s->seg_offset[segment], cols,
-        alphas, total, dst0, dst1);
+    const uint64_t kind = s->seg_kind[segment];
+    hipLaunchKernelGGL(kind == bj::lib::KIND   ? bj::gate_terms_kernel<bj::lib::Program>
+                       : kind == bj::p2g::KIND ? bj::gate_terms_kernel<bj::p2g::Program>
+                                               : bj::gate_terms_kernel<bj::Interpreter>,
+                       dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, bj::S(stream),
+                       s->image_d + s->seg_offset[segment], cols, alphas, total, dst0, dst1);
     return bj::ok_or(hipGetLastError(), "quotient gate terms");
 }
 
@@ -661,10 +723,14 @@ int bj_gate_set_satisfied_d(const void* set, uint32_t segment, const uint64_t* v
     const uint64_t* seg = s->image_d + s->seg_offset[segment];
     if (begin) hipLaunchKernelGGL(bj::gate_check_begin_kernel, dim3(1), dim3(bj::GC_WAVE), 0, st, status);
     const size_t blocks = (size_t)((n_rows + bj::GT_THREADS - 1) / bj::GT_THREADS);
-    const bool native = s->seg_kind[segment] != 0;
-    hipLaunchKernelGGL(native ? bj::gate_check_kernel<bj::p2g::Program> : bj::gate_check_kernel<bj::Interpreter>,
+    const uint64_t kind = s->seg_kind[segment];
+    hipLaunchKernelGGL(kind == bj::lib::KIND   ? bj::gate_check_kernel<bj::lib::Program>
+                       : kind == bj::p2g::KIND ? bj::gate_check_kernel<bj::p2g::Program>
+                                               : bj::gate_check_kernel<bj::Interpreter>,
                        dim3((unsigned)blocks), dim3(bj::GT_THREADS), 0, st, seg, cols, row_begin, n_rows, status);
-    hipLaunchKernelGGL(native ? bj::gate_value_kernel<bj::p2g::Program> : bj::gate_value_kernel<bj::Interpreter>,
+    hipLaunchKernelGGL(kind == bj::lib::KIND   ? bj::gate_value_kernel<bj::lib::Program>
+                       : kind == bj::p2g::KIND ? bj::gate_value_kernel<bj::p2g::Program>
+                                               : bj::gate_value_kernel<bj::Interpreter>,
                        dim3(1), dim3(bj::GC_WAVE), 0, st, seg, cols, row_begin, n_rows, status);
     return bj::ok_or(hipGetLastError(), "gate set satisfiability check");
 }

@@ -707,12 +707,13 @@ int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out);
  *   [0] 0x3153455441474A42 ("BJGATES1")  [1] segments S  [2 .. 2 + S) word offset of each segment
  *   segment:    [0] gates G  [1] instructions I  [2] writes W  [3] immediates M  [4] alpha base (the
  *               terms of the segments before it)  [5] terms  [6] deepest selector path  [7] kind:
- *               0 interpreted, 1 native Poseidon2 flattened gate (below), then
+ *               0 interpreted, 1 native Poseidon2 flattened gate, 3 library gates (both below;
+ *               2 is no kind), then
  *               G descriptors of 8 words, I instructions, W writes, M immediates
  *   descriptor: [0] instruction begin | end << 32  [1] write begin | end << 32 (in push order)
  *               [2] num_repetitions | path length << 32  [3] path mask, bit i set: column i, clear:
  *               1 - column i  [4] variables base | per repetition << 32  [5] witnesses, [6]
- *               constants likewise  [7] 0 (native segment: num_witness_columns_used)
+ *               constants likewise  [7] 0 (native Poseidon2 segment: num_witness_columns_used)
  *   instruction: opcode | destination slot << 8 | operand a << 16 | operand b << 40
  *   operand (24 bits): kind << 21 | index; kinds 0 VariablePoly, 1 WitnessPoly, 2 ConstantPoly,
  *               3 slot, 4 immediate (index into the segment's M words); a write is one operand
@@ -738,6 +739,17 @@ int bj_vanishing_inverses_h(uint32_t log_n, uint32_t log_q, uint64_t* out);
  * least 130 - nw and witnesses per repetition at least nw; terms = 118 * repetitions.  The magic is
  * unchanged, and an image without native segments is word for word what it was.
  *
+ * Library segments, kind 3.  The library holds straight-line code for the gates every circuit of the
+ * reference uses, generated from their captures (bj_gate_library_find_h names them).  A segment of
+ * kind 3 holds 1 .. BJ_GATE_MAX_GATES such gates and no program: I = W = M = 0, [4], [5] and [6] as for
+ * every segment.  A descriptor's [0] is the library id (high half 0), [1] is 0 | terms per repetition
+ * << 32 with no writes behind it, [2] .. [6] are the placement words, [7] is 0.  The gate computes what
+ * the interpreter computes on the capture it was generated from -- the caller compares the digest of
+ * its own capture with the library's before it names an entry -- so an image may use either kind for
+ * such a gate, with the same columns, challenges and results; which is faster is DESIGN 4.12.3's
+ * subject.  Refused: a program area that is not empty, an id outside the table, a term count that is
+ * not the entry's, word [7] != 0, and sums of the head that do not add up.
+ *
  * Checks, all on the host and none per point: the magic, every range, the caps, an operand outside
  * its space, a slot read before it is written in its gate, a term count or alpha base that does
  * not add up, and opcode 6, Relation::Inverse.  No evaluator in cs/gates records Inverse: its three
@@ -759,6 +771,16 @@ int bj_gate_set_check_h(const uint64_t* image, size_t words, uint64_t* need);
  * columns (106).  Added after 2.6; detect by symbol (bj_abi_version() is unchanged): a library
  * without it refuses word [7] != 0.  Host only.  BJ_EINVAL: an unknown kind, null out. */
 int bj_gate_native_info_h(uint32_t kind, uint64_t* out);
+
+/* A library gate by the name of its evaluator (fma_gate_in_base_without_constant, boolean_constraint,
+ * constants_allocator, reduction_gate_4, selection_gate, zero_check_variable, zero_check_witness,
+ * dot_product_gate_4, conditional_swap_gate_1): out[0] the id for descriptor word [0] of a kind-3
+ * segment, [1] the terms per repetition, [2], [3], [4] the variable, witness and constant columns one
+ * repetition reads (highest index + 1), [5] the 64-bit digest of the capture the code was generated
+ * from (FNV-1a-64 over the relations and writes; INTEGRATION.md "Library gates" gives the bytes).
+ * Added after 2.6; detect by symbol (bj_abi_version() is unchanged): a library without it refuses
+ * kind 3.  Host only.  BJ_EINVAL: an unknown or null name, null out. */
+int bj_gate_library_find_h(const char* name, uint64_t* out);
 
 /* bj_gate_set_check_h, then the one upload: allocates words * 8 bytes on the current device, copies
  * the image and synchronises.  *set is the handle the evaluation takes; it keeps the device buffer

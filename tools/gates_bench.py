@@ -19,6 +19,11 @@ kernel's work does not depend on the values.  Timed with HIP events on the strea
   78.6 T lane issue slots/s of the GPU.  Counted from the programs: the relations of every
   repetition, two products and two additions per term for the challenge, the selector path and
   the two products by the selector per gate.  Decode, addressing and LDS traffic are not in it.
+* library: the same placements, columns and challenges through GateSet(placements,
+  native_library=True), whose gates run the generated straight-line walks (csrc/gates_library.hpp).
+  Three rounds alternate the interpreted and the library set (10 calls each per round); both medians,
+  every round's time, the launches and the ratio to the interpreted median are reported.  The first
+  round of the interpreted set is "gate_terms", as before.
 
 usage: python tools/gates_bench.py [log_n=20] [n_vars=130] [q=8]   (prints one JSON line)
 """
@@ -100,7 +105,15 @@ def main():
     def gate_terms():
         G.evaluate_gate_terms(gate_set, variables, None, constants, alphas, q, dst[0], dst[1])
 
-    t = timed(torch, gate_terms, 10)
+    library_set = G.GateSet(placements, native_library=True)
+    kinds = [library_set.image[library_set.image[2 + s] + 7] for s in range(library_set.num_segments)]
+
+    def library_terms():
+        G.evaluate_gate_terms(library_set, variables, None, constants, alphas, q, dst[0], dst[1])
+
+    rounds = [(timed(torch, gate_terms, 10), timed(torch, library_terms, 10)) for _ in range(3)]
+    t = rounds[0][0]
+    t_int, t_lib = (sorted(r[i] for r in rounds)[1] for i in range(2))
     nbytes = (n_vars + n_consts + 4) * total * 8
     words = nbytes // 16
     src1 = cols.reshape(-1)
@@ -131,6 +144,13 @@ def main():
                                                        if o.kind.endswith("Poly")) for pl in placements)},
             "slot_floor": {"slots_per_product": MUL_SLOTS, "slots_per_addition": ADD_SLOTS, "slots_per_point": slots,
                            "ms": floor * 1e3, "frac_of_slot_floor": floor / t},
+        },
+        "library": {
+            "ms": t_lib * 1e3, "interpreted_ms": t_int * 1e3, "vs_interpreted": t_lib / t_int,
+            "rounds_ms": {"interpreted": [r[0] * 1e3 for r in rounds], "library": [r[1] * 1e3 for r in rounds]},
+            "launches": library_set.num_segments, "segment_kinds": kinds,
+            "achieved": nbytes / t_lib / 1e9, "unit": "GB/s", "vs_copy": nbytes / t_lib / 1e9 / copy_gbs,
+            "frac_of_slot_floor": floor / t_lib,
         },
     }
     print(json.dumps(line))
