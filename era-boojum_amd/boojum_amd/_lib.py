@@ -42,6 +42,37 @@ class ShardedQueryOracleDesc(ctypes.Structure):
 assert ctypes.sizeof(ShardedQueryOracleDesc) == 56
 _sqop = ctypes.POINTER(ShardedQueryOracleDesc)
 
+
+DEEP_MAX_GROUPS, DEEP_MAX_POINTS, DEEP_MAX_TERMS = 8, 8, 16  # BJ_DEEP_MAX_*
+
+
+class DeepGroup(ctypes.Structure):
+    """bj_deep_group_t (include/boojum_mi355x.h), 24 bytes."""
+    _fields_ = [("cols", _vp), ("col_stride", _sz), ("n_cols", _u32), ("reserved", _u32)]
+
+
+class DeepPoint(ctypes.Structure):
+    """bj_deep_point_t, 32 bytes."""
+    _fields_ = [("at0", _u64), ("at1", _u64), ("k0", _u64), ("k1", _u64)]
+
+
+class DeepTerm(ctypes.Structure):
+    """bj_deep_term_t, 24 bytes."""
+    _fields_ = [("group", _u32), ("first_col", _u32), ("n_cols", _u32), ("point", _u32), ("gamma_offset", _u32),
+                ("reserved", _u32)]
+
+
+class DeepCodewordDesc(ctypes.Structure):
+    """bj_deep_codeword_t, 904 bytes."""
+    _fields_ = [("groups", DeepGroup * DEEP_MAX_GROUPS), ("points", DeepPoint * DEEP_MAX_POINTS),
+                ("terms", DeepTerm * DEEP_MAX_TERMS), ("n_groups", _u32), ("n_points", _u32), ("n_terms", _u32),
+                ("log_domain", _u32), ("gammas", _vp), ("n_gammas", _sz), ("row0", _sz), ("n_rows", _sz),
+                ("dst0", _vp), ("dst1", _vp), ("accumulate", ctypes.c_int32), ("reserved", _u32)]
+
+
+assert ctypes.sizeof(DeepCodewordDesc) == 904
+_dcp = ctypes.POINTER(DeepCodewordDesc)
+
 # name -> argtypes (restype int unless noted).  Every symbol the header declares.
 SIGNATURES = {
     "bj_last_error": ([], ctypes.c_char_p),
@@ -111,6 +142,7 @@ SIGNATURES = {
     "bj_barycentric_weights_d": ([_u32, _u64, _u64, _u64, _vp, _vp, _vp], _int),
     "bj_evaluate_at_d": ([_vp, _u32, _sz, _u32, _vp, _vp, _vp, _vp], _int),
     "bj_deep_quotient_d": ([_vp, _u32, _sz, _vp, _u64, _u64, _u64, _u64, _u32, _sz, _sz, _vp, _vp, _int, _vp], _int),
+    "bj_deep_codeword_d": ([_dcp, _vp], _int),
     "bj_copy_permutation_d": ([_vp, _sz, _vp, _sz, _u32, _u32, _u64p, _u64, _u64, _u64, _u64, _u32, _vp, _sz, _vp,
                                _vp], _int),
     "bj_lookup_encoding_d": ([ctypes.POINTER(_vp), _u32, _u64p, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp], _int),
@@ -148,7 +180,7 @@ SIGNATURES = {
 }
 
 # Added after 2.6 and detected by symbol: a library without one of these still loads.
-OPTIONAL = ("bj_gate_native_info_h", "bj_gate_library_find_h")
+OPTIONAL = ("bj_gate_native_info_h", "bj_gate_library_find_h", "bj_deep_codeword_d")
 
 
 class CommInfo(ctypes.Structure):

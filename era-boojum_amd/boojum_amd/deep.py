@@ -7,7 +7,9 @@
   of many columns in one call (bj_evaluate_at_d).
 * Quotening (prover.rs:1823-2050, quotening_operation_in_extension :2523-2706): for every point x
   of the whole LDE domain, sum_j c^j (f_j(x) - f_j(at)) / (x - at), accumulated over the opening
-  points z, z * omega, 0 and the public-input rows (bj_deep_quotient_d, one call per point).
+  points z, z * omega, 0 and the public-input rows (bj_deep_quotient_d, one call per point and
+  source tensor), or all of them over every source tensor in one launch (`deep_codeword`,
+  bj_deep_codeword_d).
 
 The kernel sees base columns only.  `quotening_plan` folds the sources of one opening point --
 base columns, or Ext2 polynomials held as two base columns (c0, c1) -- into one Ext2 coefficient
@@ -22,7 +24,7 @@ ch_j * u to the c1 column's, K = sum_j ch_j v_j.  That is host arithmetic on sin
 import numpy as np
 import torch
 
-from ._lib import call
+from ._lib import DEEP_MAX_GROUPS, DEEP_MAX_POINTS, DEEP_MAX_TERMS, DeepCodewordDesc, call
 from .field import EXT2_NON_RESIDUE, P, col_view, ext2_mul, ext2_mul_by_u, log2_exact, stream_of, to_device, to_host
 
 
@@ -112,3 +114,83 @@ def quotening_operation_in_extension(dst_c0, dst_c1, storage, entries, at, log_d
     call("bj_deep_quotient_d", ptr, c, stride, g.data_ptr() if c else 0, k[0], k[1], at[0] % P, at[1] % P,
          log_domain, row0, n_rows, dst_c0.data_ptr(), dst_c1.data_ptr(), 1 if accumulate else 0, stream_of(dst_c0))
     return dst_c0, dst_c1
+
+
+def codeword_terms(group_cols, points):
+    """The terms of one bj_deep_codeword_d call, host arithmetic only.  group_cols: the column
+    count of every group; points: [(at, entries)], entries [(group, col, is_ext, challenge,
+    value_at)] in challenge order -- quotening_plan's entries with the group in front.  Per point,
+    in order, and per group it has sources in, in group order: quotening_plan over that group's
+    entries, trimmed to the column range [first, first + count) the entries touch.  Returns
+    (terms, gammas, ks): terms [(group, first_col, n_cols, point, gamma_offset)] sorted by point,
+    gammas the flat list of Ext2 coefficients the offsets index, ks the Ext2 constant of every
+    point (the sum over its groups)."""
+    terms, gammas, ks = [], [], []
+    for p, (_, entries) in enumerate(points):
+        k = (0, 0)
+        for g, n_cols in enumerate(group_cols):
+            mine = [e[1:] for e in entries if e[0] == g]
+            if not mine:
+                continue
+            full, kg = quotening_plan(n_cols, mine)
+            k = ((k[0] + kg[0]) % P, (k[1] + kg[1]) % P)
+            first = min(col for col, _, _, _ in mine)
+            end = max(col + (2 if is_ext else 1) for col, is_ext, _, _ in mine)
+            terms.append((g, first, end - first, p, len(gammas)))
+            gammas += full[first:end]
+        for e in entries:
+            if not 0 <= e[0] < len(group_cols):
+                raise ValueError("group %d outside [0, %d)" % (e[0], len(group_cols)))
+        ks.append(k)
+    return terms, gammas, ks
+
+
+def codeword_descriptor(groups, points, terms, ks, gammas_ptr, n_gammas, log_domain, row0, n_rows, dst0, dst1,
+                        accumulate):
+    """bj_deep_codeword_t from plain values.  groups: [(ptr, n_cols, col_stride)]; points: [(at, _)];
+    terms and ks: codeword_terms'; the pointers are integers (0 for NULL)."""
+    if len(groups) > DEEP_MAX_GROUPS or len(points) > DEEP_MAX_POINTS or len(terms) > DEEP_MAX_TERMS:
+        raise ValueError("%d groups, %d points, %d terms exceed the caps %d, %d, %d of one call"
+                         % (len(groups), len(points), len(terms), DEEP_MAX_GROUPS, DEEP_MAX_POINTS, DEEP_MAX_TERMS))
+    d = DeepCodewordDesc()
+    for i, (ptr, n_cols, stride) in enumerate(groups):
+        d.groups[i].cols, d.groups[i].n_cols, d.groups[i].col_stride = ptr or None, n_cols, stride
+    for i, ((at, _), k) in enumerate(zip(points, ks)):
+        d.points[i].at0, d.points[i].at1, d.points[i].k0, d.points[i].k1 = at[0] % P, at[1] % P, k[0] % P, k[1] % P
+    for i, (g, first, count, p, off) in enumerate(terms):
+        t = d.terms[i]
+        t.group, t.first_col, t.n_cols, t.point, t.gamma_offset = g, first, count, p, off
+    d.n_groups, d.n_points, d.n_terms, d.log_domain = len(groups), len(points), len(terms), log_domain
+    d.gammas, d.n_gammas, d.row0, d.n_rows = gammas_ptr or None, n_gammas, row0, n_rows
+    d.dst0, d.dst1, d.accumulate = dst0 or None, dst1 or None, 1 if accumulate else 0
+    return d
+
+
+def deep_codeword(groups, points, log_domain, row0=0, out=None, accumulate=False):
+    """Every opening point of the codeword over rows [row0, row0 + rows) of the flat bit-reversed
+    domain of 2^log_domain points in one launch (bj_deep_codeword_d): what one
+    quotening_operation_in_extension per (group, point) leaves, word for word.  groups: (C, rows)
+    device column views over the same row window (an oracle's LDE, flattened); points: [(at,
+    entries)] as codeword_terms takes them; out: None or the pair (dst_c0, dst_c1) of (rows,)
+    device columns.  The coefficients of all terms go to the device in one copy.  Returns
+    (dst_c0, dst_c1)."""
+    import ctypes
+    views = [col_view(g) for g in groups]
+    if out is None:
+        if not views:
+            raise ValueError("without groups the row count comes from `out`")
+        if accumulate:
+            raise ValueError("accumulate needs `out`")
+        buf = torch.empty((2, views[0][2]), dtype=torch.int64, device=views[0][0].device)
+        out = (buf[0], buf[1])
+    dst0, dst1 = out
+    n_rows = dst0.shape[-1]
+    if dst1.shape[-1] != n_rows or any(v[2] != n_rows for v in views):
+        raise ValueError("groups and dst row counts differ")
+    terms, gammas, ks = codeword_terms([v[1] for v in views], points)
+    g = to_device(np.array(gammas, dtype=np.uint64).reshape(-1), dst0.device) if gammas else None
+    d = codeword_descriptor([(v[0].data_ptr(), v[1], v[3]) for v in views], points, terms, ks,
+                            g.data_ptr() if gammas else 0, len(gammas), log_domain, row0, n_rows, dst0.data_ptr(),
+                            dst1.data_ptr(), accumulate)
+    call("bj_deep_codeword_d", ctypes.byref(d), stream_of(dst0))
+    return dst0, dst1

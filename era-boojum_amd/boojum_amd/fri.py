@@ -25,6 +25,36 @@ from .fft import bitreverse_enumeration_inplace, ifft_natural_to_natural
 from .field import GENERATOR, P, ext2_square, log2_exact, stream_of, to_host
 
 
+def compute_fri_schedule(security_bits, cap_size, pow_bits, rate_log_two, initial_degree_log_two):
+    """compute_fri_schedule (prover.rs:2281-2372) -> (new_pow_bits, num_queries, schedule,
+    final_degree).  PoW bits that buy no whole query are dropped; folding goes by 3 while it can,
+    then by 2 or 1, down to max(1, cap_size >> rate_log_two) coefficients, and stops before a tree
+    would be no larger than its cap.  ValueError where the reference asserts."""
+    if security_bits <= pow_bits:
+        raise ValueError("security_bits must exceed pow_bits (prover.rs:2293)")
+    if rate_log_two < 1:
+        raise ValueError("rate_log_two is at least 1")
+    log2_exact(cap_size)
+    new_pow_bits = pow_bits
+    short = (security_bits - pow_bits) % rate_log_two
+    if short and new_pow_bits >= rate_log_two - short:
+        new_pow_bits -= rate_log_two - short        # there is no point to do so much PoW
+    num_queries = -(-(security_bits - new_pow_bits) // rate_log_two)
+    stop_log = log2_exact(max(1, cap_size >> rate_log_two))
+    cap_log = log2_exact(cap_size)
+    degree = initial_degree_log_two
+    schedule = []
+    while degree > stop_log and degree + rate_log_two > cap_log:
+        step = min(3, degree - stop_log)
+        degree -= step
+        schedule.append(step)
+        if step == 1:
+            break
+    if degree + rate_log_two < cap_log:
+        raise ValueError("the last tree is smaller than the cap (prover.rs:2364)")
+    return new_pow_bits, num_queries, schedule, 1 << degree
+
+
 def challenge_powers(challenge, reduction_degree_log_2):
     """[alpha, alpha^2, alpha^4, ...] as fri/mod.rs:206-226 builds them for one reduction step."""
     out = [(challenge[0] % P, challenge[1] % P)]
@@ -175,9 +205,9 @@ def do_fri(c0, c1, transcript, interpolation_log2s_schedule, lde_degree, cap_siz
     monomials, witnessed c0 then c1.  The only host round trips are each cap, and one copy that
     brings the monomials and the low-degree flags.  Returns FriOracles.  ValueError where the
     reference asserts: a schedule entry outside 1..3, final_degree == 0.
-    Outside this function: Blake2s / Keccak transcripts and BoolsBuffer, the schedule computation
-    (compute_fri_schedule), the DEEP-to-FRI glue, and hashing the next oracle's leaves inside the
-    fold kernel."""
+    Outside this function: Blake2s / Keccak transcripts and hashing the next oracle's leaves inside
+    the fold kernel; the schedule is `compute_fri_schedule`, and openings.prove_openings runs the
+    DEEP codeword into this call and the queries out of it."""
     from .merkle import MerkleTreeWithCap
     schedule = [int(s) for s in interpolation_log2s_schedule]
     if not schedule:

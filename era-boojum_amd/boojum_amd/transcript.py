@@ -8,7 +8,10 @@ single permutation on the device): a transcript absorbs a few caps and field ele
 and what it feeds on (caps, evaluations, the final FRI monomials) is already on the host when it
 is witnessed.  fri.do_fri takes any object with these three methods.
 
-Not here: the Blake2s and Keccak transcripts (transcript.rs:153-367) and BoolsBuffer (:369-417).
+`BoolsBuffer` (transcript.rs:369-417) draws the query indices' bits from it.
+
+Not here: the Blake2s and Keccak transcripts (transcript.rs:153-367), and with them BoolsBuffer's
+byte branch.
 """
 from .field import P
 from .merkle import Poseidon2Sponge
@@ -58,3 +61,29 @@ class Poseidon2Transcript:
 
     def get_multiple_challenges(self, n):
         return [self.get_challenge() for _ in range(n)]
+
+
+class BoolsBuffer:
+    """BoolsBuffer (transcript.rs:369-417), the branch of an algebraic transcript: when fewer bits
+    are left than asked for, one more challenge gives its 64 - max_needed least significant bits
+    (of the reduced u64, lowest first), appended to what is left."""
+
+    def __init__(self, max_needed):
+        if not 0 <= max_needed <= 64:
+            raise ValueError("max_needed outside 0..64")
+        self.available = []
+        self.max_needed = max_needed
+
+    def get_bits(self, transcript, num_bits):
+        while len(self.available) < num_bits:
+            if self.max_needed == 64:
+                raise ValueError("a challenge gives no bits with max_needed = 64")
+            el = int(transcript.get_challenge()) % P
+            self.available += [bool((el >> i) & 1) for i in range(64 - self.max_needed)]
+        give, self.available = self.available[:num_bits], self.available[num_bits:]
+        return give
+
+
+def u64_from_lsb_first_bits(bits):
+    """The integer whose bit i is bits[i] (prover.rs:2272-2279)."""
+    return sum(int(b) << i for i, b in enumerate(bits))

@@ -6,6 +6,8 @@
 //   (utils.rs:1085-1158) for many columns at once, the sums of prover.rs:1501-1780.
 // * bj_deep_quotient_d: one opening point of quotening_operation_in_extension
 //   (prover.rs:2523-2706, driven by :1823-2050) over a row window of the flat bit-reversed domain.
+// * bj_deep_codeword_d: every opening point over several column groups in one launch, with one
+//   shared x and one base-field inversion per row pair.
 //
 // GoldilocksExt2 is (c0, c1) with u^2 = 7 (field/goldilocks/extension.rs:14-40).  The kernels see
 // base columns only: the caller folds every source of an opening point, base or Ext2, into one
@@ -251,6 +253,170 @@ __global__ __launch_bounds__(256) void deep_quotient_kernel(
     }
 }
 
+// ------------------------------------------------------------------ the codeword in one launch
+// Every opening point of bj_deep_codeword_d.  The arguments travel by value: a term is a column
+// range of one group with its coefficients, the terms of point p are [term_end[p - 1], term_end[p]).
+constexpr uint32_t CW_POINTS = BJ_DEEP_MAX_POINTS;
+constexpr uint32_t CW_TERMS = BJ_DEEP_MAX_TERMS;
+struct CwTerm {
+    const uint64_t* base;    // the range's first column, window-relative
+    size_t stride;
+    const uint64_t* gammas;  // n_cols x 2
+    uint32_t n_cols, pad;
+};
+struct CwPoint {
+    uint64_t at0, at1, s7, k0, k1;  // canonical; s7 = 7 at1^2
+};
+struct CwArgs {
+    CwTerm term[CW_TERMS];
+    CwPoint point[CW_POINTS];
+    uint32_t term_end[CW_POINTS];
+    uint64_t wpow[32];  // w_{2^log_domain}^(2^b)
+    uint32_t n_points, pair_bits;
+};
+static_assert(sizeof(CwArgs) <= 3600, "the kernel arguments hold 4096 bytes");
+static_assert(sizeof(bj_deep_codeword_t) == 904, "the descriptor of the C ABI");
+
+// deep_quotient_kernel's thread (the row pair (x, -x), the same loads, the same column walk), with
+// x computed once from the powers in the arguments and shared by the points, and one inversion for
+// all of them: phase 1 takes the product of the norms of x - at_p and -x - at_p for every p, inverts
+// the product of those and unwinds it into one inverse per point (Montgomery's trick, unrolled over
+// the cap so the arrays stay in registers); phase 2 walks the points, each term's columns as the
+// one-point kernel does, splits the point's inverse between its two rows with the norms computed
+// again, multiplies and adds into one Ext2 sum per row, written once.
+template <bool V16>
+__global__ __launch_bounds__(256) void deep_codeword_kernel(CwArgs a, size_t row0, size_t n_rows, size_t n_pairs,
+                                                            uint64_t* __restrict__ dst0, uint64_t* __restrict__ dst1,
+                                                            int accumulate) {
+    const size_t t = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (t >= n_pairs) return;
+    const size_t pair = (row0 >> 1) + t;
+    const ptrdiff_t rel = (ptrdiff_t)(2 * pair) - (ptrdiff_t)row0;
+    const bool in_e = V16 || (rel >= 0 && (size_t)rel < n_rows);
+    const bool in_o = V16 || (size_t)(rel + 1) < n_rows;
+    auto load = [&](const uint64_t* col, uint64_t& fe, uint64_t& fo) {
+        if constexpr (V16) {
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(col + rel);
+            fe = v.x;
+            fo = v.y;
+        } else {
+            fe = in_e ? col[rel] : 0;
+            fo = in_o ? col[rel + 1] : 0;
+        }
+    };
+    // x = 7 w^(bitrev(pair))
+    uint64_t x = gl::GENERATOR;
+    {
+        const uint32_t e = gl::bitrev32((uint32_t)pair, a.pair_bits);
+        for (uint32_t b = 0; b < a.pair_bits; b++) x = gl::mul(x, (e >> b) & 1 ? a.wpow[b] : 1);
+    }
+    // phase 1: ip[p] = 1 / (norm(x - at_p) norm(-x - at_p)), a row outside the window counting as norm 1
+    auto norms = [&](uint32_t p, uint64_t& de, uint64_t& xa, uint64_t& ne, uint64_t& no) {
+        de = gl::sub(x, a.point[p].at0);
+        xa = gl::add(x, a.point[p].at0);  // the odd row's c0 is -xa
+        ne = in_e ? gl::sub(gl::mul(de, de), a.point[p].s7) : 1;
+        no = in_o ? gl::sub(gl::mul(xa, xa), a.point[p].s7) : 1;
+    };
+    uint64_t ip[CW_POINTS];
+    {
+        uint64_t nn[CW_POINTS];
+        uint64_t run = 1;
+#pragma unroll
+        for (uint32_t p = 0; p < CW_POINTS; p++) {
+            ip[p] = nn[p] = 1;
+            if (p < a.n_points) {  // wave-uniform
+                uint64_t de, xa, ne, no;
+                norms(p, de, xa, ne, no);
+                nn[p] = gl::mul(ne, no);
+                ip[p] = run;  // the product of the points before p, for now
+                run = gl::mul(run, nn[p]);
+            }
+        }
+        uint64_t inv = inv_chain(run);
+#pragma unroll
+        for (int p = CW_POINTS - 1; p >= 0; p--) {
+            if ((uint32_t)p < a.n_points) {
+                ip[p] = gl::mul(inv, ip[p]);
+                inv = gl::mul(inv, nn[p]);
+            }
+        }
+    }
+    // phase 2
+    uint64_t q[4] = {0, 0, 0, 0};  // even row (c0, c1), odd row (c0, c1)
+    uint32_t ti = 0;
+    for (uint32_t p = 0; p < a.n_points; p++) {
+        uint64_t acc[4] = {0, 0, 0, 0};
+        const uint32_t te = a.term_end[p];
+        for (; ti < te; ti++) {
+            const uint64_t* __restrict__ cols = a.term[ti].base;
+            const uint64_t* __restrict__ gammas = a.term[ti].gammas;
+            const size_t col_stride = a.term[ti].stride;
+            const uint32_t n_cols = a.term[ti].n_cols;
+            uint32_t c = 0;
+            for (; c + DQ_UNROLL <= n_cols; c += DQ_UNROLL) {
+                uint64_t fe[DQ_UNROLL], fo[DQ_UNROLL];
+#pragma unroll
+                for (uint32_t j = 0; j < DQ_UNROLL; j++) load(cols + (size_t)(c + j) * col_stride, fe[j], fo[j]);
+#pragma unroll
+                for (uint32_t j = 0; j < DQ_UNROLL; j++)
+                    fma_pair(fe[j], fo[j], gammas[2 * (c + j)], gammas[2 * (c + j) + 1], acc);
+            }
+            for (; c < n_cols; c++) {
+                uint64_t fe, fo;
+                load(cols + (size_t)c * col_stride, fe, fo);
+                fma_pair(fe, fo, gammas[2 * c], gammas[2 * c + 1], acc);
+            }
+        }
+        // the point's inverse: a select chain on the wave-uniform p, so ip stays in registers
+        uint64_t ipp = ip[0];
+#pragma unroll
+        for (uint32_t k = 1; k < CW_POINTS; k++) ipp = p == k ? ip[k] : ipp;
+        uint64_t de, xa, ne, no;
+        norms(p, de, xa, ne, no);
+        const uint64_t iep = gl::mul(ipp, no), iop = gl::mul(ipp, ne), at1 = a.point[p].at1;
+        // 1 / (d0 - at1 u) = (d0 + at1 u) / norm
+        const E2 inv_e = {gl::mul(de, iep), gl::mul(at1, iep)};
+        const E2 inv_o = {gl::mul(neg(xa), iop), gl::mul(at1, iop)};
+        const E2 me = {gl::sub(acc[0], a.point[p].k0), gl::sub(acc[1], a.point[p].k1)};
+        const E2 mo = {gl::sub(acc[2], a.point[p].k0), gl::sub(acc[3], a.point[p].k1)};
+        const E2 re = mul_x4(me, inv_e), ro = mul_x4(mo, inv_o);
+        q[0] = gl::add(q[0], re.c0);
+        q[1] = gl::add(q[1], re.c1);
+        q[2] = gl::add(q[2], ro.c0);
+        q[3] = gl::add(q[3], ro.c1);
+    }
+    if constexpr (V16) {
+        ulonglong2* p0 = reinterpret_cast<ulonglong2*>(dst0 + rel);
+        ulonglong2* p1 = reinterpret_cast<ulonglong2*>(dst1 + rel);
+        if (accumulate) {
+            const ulonglong2 u = *p0, v = *p1;
+            q[0] = gl::add(q[0], u.x);
+            q[2] = gl::add(q[2], u.y);
+            q[1] = gl::add(q[1], v.x);
+            q[3] = gl::add(q[3], v.y);
+        }
+        *p0 = make_ulonglong2(gl::canon(q[0]), gl::canon(q[2]));
+        *p1 = make_ulonglong2(gl::canon(q[1]), gl::canon(q[3]));
+    } else {
+        if (in_e) {
+            if (accumulate) {
+                q[0] = gl::add(q[0], dst0[rel]);
+                q[1] = gl::add(q[1], dst1[rel]);
+            }
+            dst0[rel] = gl::canon(q[0]);
+            dst1[rel] = gl::canon(q[1]);
+        }
+        if (in_o) {
+            if (accumulate) {
+                q[2] = gl::add(q[2], dst0[rel + 1]);
+                q[3] = gl::add(q[3], dst1[rel + 1]);
+            }
+            dst0[rel + 1] = gl::canon(q[2]);
+            dst1[rel + 1] = gl::canon(q[3]);
+        }
+    }
+}
+
 // ------------------------------------------------------------------ launchers
 hipError_t launch_pow_table(uint64_t* tab, uint64_t w, uint64_t scale, hipStream_t st) {
     hipLaunchKernelGGL(pow_table_kernel, dim3(POW_TAB_WORDS / 256), dim3(256), 0, st, tab, w, scale);
@@ -331,6 +497,68 @@ hipError_t launch_deep_quotient(const uint64_t* cols, uint32_t n_cols, size_t co
     return hipGetLastError();
 }
 
+// NULL when the descriptor's shape is sound (what can be said without looking at n_rows)
+const char* bad_codeword(const bj_deep_codeword_t& d) {
+    if (d.n_groups > BJ_DEEP_MAX_GROUPS) return "bj_deep_codeword_d: more than BJ_DEEP_MAX_GROUPS groups";
+    if (d.n_points > BJ_DEEP_MAX_POINTS) return "bj_deep_codeword_d: more than BJ_DEEP_MAX_POINTS points";
+    if (d.n_terms > BJ_DEEP_MAX_TERMS) return "bj_deep_codeword_d: more than BJ_DEEP_MAX_TERMS terms";
+    if (d.log_domain > 32) return "log_domain exceeds the 2-adicity (32) of the field";
+    const size_t domain = (size_t)1 << d.log_domain;
+    if (d.n_rows > domain || d.row0 > domain - d.n_rows) return "bj_deep_codeword_d: row0 + n_rows exceeds 2^log_domain";
+    for (uint32_t t = 0; t < d.n_terms; t++) {
+        const bj_deep_term_t& m = d.terms[t];
+        if (m.group >= d.n_groups) return "bj_deep_codeword_d: a term names a missing group";
+        if (m.point >= d.n_points) return "bj_deep_codeword_d: a term names a missing point";
+        const uint32_t gc = d.groups[m.group].n_cols;
+        if (m.first_col > gc || m.n_cols > gc - m.first_col) return "bj_deep_codeword_d: a term's columns lie outside its group";
+        if (m.gamma_offset > d.n_gammas || m.n_cols > d.n_gammas - m.gamma_offset)
+            return "bj_deep_codeword_d: a term's coefficients lie outside gammas";
+        if (t && m.point < d.terms[t - 1].point) return "bj_deep_codeword_d: terms are not sorted by point";
+    }
+    return nullptr;
+}
+const char* bad_codeword_pointers(const bj_deep_codeword_t& d) {
+    if (!d.dst0 || !d.dst1) return "bj_deep_codeword_d: null dst";
+    if (d.n_gammas && !d.gammas) return "bj_deep_codeword_d: null gammas";
+    for (uint32_t g = 0; g < d.n_groups; g++) {
+        if (d.groups[g].n_cols && !d.groups[g].cols) return "bj_deep_codeword_d: null cols";
+        if (d.groups[g].n_cols && d.groups[g].col_stride < d.n_rows) return "bj_deep_codeword_d: col_stride < n_rows";
+    }
+    return nullptr;
+}
+
+// d has passed both checks and n_rows > 0
+hipError_t launch_deep_codeword(const bj_deep_codeword_t& d, hipStream_t st) {
+    CwArgs a = {};
+    uintptr_t align = (uintptr_t)d.dst0 | (uintptr_t)d.dst1;
+    bool even_strides = true;
+    uint32_t t = 0;
+    for (uint32_t p = 0; p < d.n_points; p++) {
+        const uint64_t at1 = gl::canon(d.points[p].at1);
+        a.point[p] = {gl::canon(d.points[p].at0), at1, gl::canon(times7(gl::mul(at1, at1))), gl::canon(d.points[p].k0),
+                      gl::canon(d.points[p].k1)};
+        for (; t < d.n_terms && d.terms[t].point == p; t++) {
+            const bj_deep_term_t& m = d.terms[t];
+            const bj_deep_group_t& g = d.groups[m.group];
+            a.term[t] = {m.n_cols ? g.cols + (size_t)m.first_col * g.col_stride : nullptr, g.col_stride,
+                         m.n_cols ? d.gammas + 2 * (size_t)m.gamma_offset : nullptr, m.n_cols, 0};
+            if (m.n_cols) align |= (uintptr_t)a.term[t].base;
+            if (m.n_cols > 1 && (g.col_stride & 1)) even_strides = false;
+        }
+        a.term_end[p] = t;
+    }
+    a.n_points = d.n_points;
+    a.pair_bits = d.log_domain ? d.log_domain - 1 : 0;
+    fill_wpow(a.wpow, d.log_domain);
+    const size_t n_pairs = ((d.row0 + d.n_rows + 1) >> 1) - (d.row0 >> 1);
+    const size_t blocks = (n_pairs + 255) / 256;  // at most 2^23
+    const bool v16 = (d.row0 & 1) == 0 && (d.n_rows & 1) == 0 && align % 16 == 0 && even_strides;
+    auto kernel = v16 ? deep_codeword_kernel<true> : deep_codeword_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, d.row0, d.n_rows, n_pairs, d.dst0, d.dst1,
+                       (int)d.accumulate);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 }  // namespace bj
@@ -370,6 +598,14 @@ int bj_deep_quotient_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride,
     const hipError_t e = bj::launch_deep_quotient(cols, n_cols, col_stride, gammas, k0, k1, at0, at1, log_domain, row0,
                                                   n_rows, dst0, dst1, accumulate, bj::S(stream));
     return bj::ok_or(e, "deep quotient");
+}
+
+int bj_deep_codeword_d(const bj_deep_codeword_t* desc, void* stream) {
+    if (!desc) return bj::set_error(BJ_EINVAL, "bj_deep_codeword_d: null descriptor");
+    if (const char* why = bj::bad_codeword(*desc)) return bj::set_error(BJ_EINVAL, why);
+    if (desc->n_rows == 0) return BJ_OK;
+    if (const char* why = bj::bad_codeword_pointers(*desc)) return bj::set_error(BJ_EINVAL, why);
+    return bj::ok_or(bj::launch_deep_codeword(*desc, bj::S(stream)), "deep codeword");
 }
 
 }  // extern "C"

@@ -542,6 +542,63 @@ int bj_deep_quotient_d(const uint64_t* cols, uint32_t n_cols, size_t col_stride,
                        size_t row0, size_t n_rows, uint64_t* dst0, uint64_t* dst1, int accumulate,
                        void* stream);
 
+/* Every opening point of the DEEP codeword in one launch (prover.rs:1823-2050): what a chain of
+ * bj_deep_quotient_d calls, one per (column group, opening point), leaves in dst, word for word
+ * for any u64 input.  Added after 2.6; detect by symbol (bj_abi_version() is unchanged).  Over
+ * rows [row0, row0 + n_rows) of the flat bit-reversed domain of 2^log_domain points, with x_L of
+ * bj_deep_quotient_d:
+ *   dst0/dst1[L - row0] (+)= sum_p (sum_{terms t of p} sum_{c < n_cols_t} gammas[gamma_offset_t + c]
+ *       * groups[group_t].cols[(first_col_t + c) * col_stride + (L - row0)] - K_p) / (x_L - at_p)
+ * A column group is one tensor of columns over the row window (an oracle's LDE); a term is a
+ * column range of one group opened at one point, with its coefficients (the caller folds sources,
+ * values and challenge powers into them as for bj_deep_quotient_d) in the one device array
+ * `gammas` of n_gammas Ext2 pairs.  Terms are sorted by point; a point with no terms contributes
+ * -K / (x - at).  The descriptor is a HOST struct and travels to the kernel by value: nothing is
+ * allocated, no table is built on the device and nothing synchronises, so the call can be captured
+ * in a HIP graph.  A thread owns the row pair (x, -x), shares x between the points, and performs
+ * one base-field inversion for all of them (the product of the norms of every x - at_p and
+ * -x - at_p); dst is written once (read once before it when accumulate = 1).  The window and
+ * alignment rule of bj_deep_quotient_d's 16-byte accesses holds for every referenced column range.
+ * n_rows = 0 is a no-op; n_points = 0 writes zeros (accumulate = 0) or leaves dst as it is.
+ * BJ_EINVAL: a null descriptor, counts over the caps, log_domain > 32, row0 + n_rows >
+ * 2^log_domain, a term naming a missing group or point, a column range outside its group, a
+ * coefficient range outside n_gammas, terms not sorted by point, and with n_rows > 0: a null dst,
+ * null cols of a group with n_cols > 0, null gammas with n_gammas > 0, col_stride < n_rows.
+ * Precondition (the reference's own, not checked): no at_p is a point of 7 * <w_{2^log_domain}>. */
+#define BJ_DEEP_MAX_GROUPS 8
+#define BJ_DEEP_MAX_POINTS 8
+#define BJ_DEEP_MAX_TERMS 16
+typedef struct bj_deep_group {
+    const uint64_t* cols; /* column 0 over the row window (device); NULL iff n_cols == 0 */
+    size_t col_stride;    /* elements between columns */
+    uint32_t n_cols;
+    uint32_t reserved;    /* 0 */
+} bj_deep_group_t;
+typedef struct bj_deep_point {
+    uint64_t at0, at1; /* the opening point */
+    uint64_t k0, k1;   /* K = sum_j ch_j * v_j over all its terms */
+} bj_deep_point_t;
+typedef struct bj_deep_term {
+    uint32_t group, first_col, n_cols; /* columns [first_col, first_col + n_cols) of groups[group] */
+    uint32_t point;
+    uint32_t gamma_offset;             /* its first coefficient, in Ext2 pairs */
+    uint32_t reserved;                 /* 0 */
+} bj_deep_term_t;
+typedef struct bj_deep_codeword {
+    bj_deep_group_t groups[BJ_DEEP_MAX_GROUPS];
+    bj_deep_point_t points[BJ_DEEP_MAX_POINTS];
+    bj_deep_term_t terms[BJ_DEEP_MAX_TERMS];
+    uint32_t n_groups, n_points, n_terms, log_domain;
+    const uint64_t* gammas; /* device, n_gammas x 2 */
+    size_t n_gammas;
+    size_t row0, n_rows;
+    uint64_t* dst0;         /* device, n_rows words each */
+    uint64_t* dst1;
+    int32_t accumulate;
+    uint32_t reserved;      /* 0 */
+} bj_deep_codeword_t;
+int bj_deep_codeword_d(const bj_deep_codeword_t* desc, void* stream);
+
 /* ------------------------------------------------------------------ stage 2 */
 /* The columns of the stage-2 oracle (prover.rs:360-438, committed at :505-554), computed from
  * witness and setup columns that stay on the device: the copy-permutation grand product with its
