@@ -33,8 +33,11 @@ package is the host-side mirror of the reference's interface for that path:
                                                              (cs/implementations/fri/mod.rs:31-682)
   transcript  Poseidon2Transcript                            (cs/implementations/transcript.rs:48-151)
   pow      PoWRunner, Blake2s256, Keccak256, NoPow, search  (cs/implementations/pow.rs, prover.rs:2107-2133)
+  openings prove_openings: the opening phase in one call     (prover.rs:1497-2266)
+  prover   prepare_setup, prove_commitments, prove: a proof from a circuit's setup and a WitnessVec
+                                                             (prover.rs:150-2266, setup_storage.rs:18-70)
 """
 from ._lib import BoojumError, load  # noqa: F401
 from .field import P, GENERATOR  # noqa: F401
 
-__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "quotient", "gates", "witness", "queries", "pow", "field", "BoojumError", "load", "P", "GENERATOR"]
+__all__ = ["fft", "lde", "merkle", "commit", "deep", "stage2", "quotient", "gates", "witness", "queries", "pow", "openings", "prover", "field", "BoojumError", "load", "P", "GENERATOR"]
